@@ -20,7 +20,12 @@ does); under torchrun the launcher's ranks are used. An RCCL barrier + synchroni
 timed region, the job time is the max over ranks, and ``value`` = frames rendered by ALL ranks /
 that time (whole-job aggregate, "scaling": "weak"); ``per_gpu_frames_per_s`` = value / N.
 
-Rank 0 at N=1 adds (``--no-extras`` skips the sweep and the backward):
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line (``ms_per_step``
+= the milliseconds one timed step took). ``--dump-outputs DIR`` also writes what the last timed
+step's final calls returned (dump_outputs below); the inputs depend only on the arguments, so two
+builds run with the same arguments can be compared output for output.
+
+With ``--full`` rank 0 at N=1 adds (``--no-extras`` skips the sweep and the backward):
   roofline        attn_fwd_kernel: algorithmic FLOPs / HIP-event launch time (every 8th launch of
                   the timed region, --event-every; its FLOPs replayed for exactly those launches),
                   PMC traffic
@@ -76,6 +81,13 @@ def parse(argv=None):
     ap.add_argument("--density", type=float, default=None,
                     help="fixed block density (min=max retain) instead of the energy rule")
     ap.add_argument("--sets", type=int, default=3, help="distinct resident q/k/v sets")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline, dense SDPA, quality, the "
+                         "other operating points, the backward and the CPU baselines (the --no-* "
+                         "options below trim that)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's final calls returned (one per resident "
+                         "set) to DIR/<name>.npy as float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
@@ -85,7 +97,10 @@ def parse(argv=None):
     ap.add_argument("--event-every", type=int, default=8,
                     help="time every N-th attention launch of the timed region with HIP events")
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)  # launcher tests
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------- launcher
@@ -270,10 +285,17 @@ def run(args):
     sets = [realistic_qkv(H, L, D, 1000 * rank + s, dev) for s in range(args.sets)]
     torch.manual_seed(1234 + rank)
 
-    def one_video():
+    # --dump-outputs: the last timed step keeps what its final calls returned, one per resident set
+    kept = [] if args.dump_outputs and rank == 0 else None
+    first_kept = max(0, calls - len(sets))
+
+    def one_video(keep=None):
         for c in range(calls):
             q, k, v = sets[c % len(sets)]
-            mod(q, k, v)
+            if keep is not None and c >= first_kept:
+                keep.append((c, mod(q, k, v)))
+            else:
+                mod(q, k, v)
 
     with torch.no_grad():
         for _ in range(args.warmup):
@@ -286,14 +308,15 @@ def run(args):
         # launch, recorded on the launch stream inside the timed region (rank 0). Each event pair
         # costs the stream ~12 us (two marker packets), so timing every launch would slow the very
         # throughput being measured by ~1 %.
-        rng_state = torch.cuda.get_rng_state(dev)
-        if rank == 0:
+        # (--full only: a plain run records no events)
+        rng_state = torch.cuda.get_rng_state(dev) if args.full else None
+        if rank == 0 and args.full:
             mod.attn_events = []
             mod.attn_event_every = args.event_every
             mod._attn_launches = 0
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            one_video()
+        for s in range(args.steps):
+            one_video(kept if s == args.steps - 1 else None)
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -345,7 +368,12 @@ def run(args):
         "mean_sparsity": round(sparsity, 4),
     }
 
-    if rank == 0:
+    if kept:
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, kept, len(sets))
+        del kept
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    elif rank == 0:
         with torch.no_grad():
             extra = measure_kernels(mod, sets, L, H, D, dev, args, events, rng_state, calls)
         result.update(extra["top"])
@@ -401,6 +429,34 @@ def run(args):
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # all arrays of one dump together (the limit is 64 MB)
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, kept, n_sets):
+    """--dump-outputs: ``kept`` = [(call index, out)] of the last timed step's final calls, one per
+    resident input set: what ``inner_attention(q, k, v)`` returned to its caller ([1,H,L,D]).
+    Each goes to ``path/out_call<c>_set<s>.npy`` as float32. An output larger than its share of
+    DUMP_BUDGET_BYTES is written as a fixed sample: the elements of the flattened array at the
+    sorted indices ``numpy.random.default_rng(DUMP_SEED).integers(0, numel, share)``, the same
+    indices for every array and every run, so two builds are compared element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(kept)
+    written = {}
+    for c, out in kept:
+        flat = out.detach().reshape(-1)
+        n = flat.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        name = f"out_call{c:03d}_set{c % n_sets}"
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+        written[name] = {"shape": list(out.shape), "elements_written": int(flat.numel()),
+                         "sampled": n > share}
+    return written
 
 
 def run_stub(args, world, rank):
