@@ -475,6 +475,107 @@ def adaptive_attention_bwd(q, k, v, dout, cfg: AdaptiveConfig, fwd: dict):
     return dq_r[:, :, inv], dk_r[:, :, inv], dv_r[:, :, inv]
 
 
+def _branch_bwd(q, k, v, out, lse, dout, w, block_mask, scale, block, rdtype):
+    """One branch of two_branch_attention_bwd in fp64: the probabilities carry the row weight ``w``
+    (w*P = w*exp(S*scale - lse)); rows with lse = +-inf or w = 0 contribute nothing. ``rdtype`` not
+    None: w*P and dS are rounded to that storage dtype before the three products, as the kernels
+    feed them to the MFMAs (dS itself is formed from the unrounded w*P). Returns fp64 (dq, dk, dv)."""
+    B, H, Lq, D = q.shape
+    Lk = k.shape[2]
+    R = (lambda t: t) if rdtype is None else (lambda t: t.to(rdtype).double())
+    qf, kf, vf, of, dof = (t.double() for t in (q, k, v, out, dout))
+    lse, w = lse.double(), w.double()
+    live = torch.isfinite(lse) & (w > 0)
+    lse_s = torch.where(live, lse, torch.zeros_like(lse))
+    w_s = torch.where(live, w, torch.zeros_like(w))
+    dq = torch.zeros(B, H, Lq, D, dtype=torch.float64)
+    dk = torch.zeros(B, H, Lk, D, dtype=torch.float64)
+    dv = torch.zeros(B, H, Lk, D, dtype=torch.float64)
+    keycol_block = torch.arange(Lk) // block
+    for i in range((Lq + block - 1) // block):
+        r0, r1 = i * block, min(Lq, (i + 1) * block)
+        s = torch.matmul(qf[:, :, r0:r1], kf.transpose(-1, -2)) * scale
+        if block_mask is not None:
+            keep = block_mask[:, :, i, :].bool()[:, :, keycol_block]
+            s = s.masked_fill(~keep[:, :, None, :], float("-inf"))
+        p = torch.exp(s - lse_s[:, :, r0:r1, None]) * w_s[:, :, r0:r1, None]
+        do = dof[:, :, r0:r1]
+        delta = (do * of[:, :, r0:r1]).sum(-1, keepdim=True)
+        ds = R(p * (torch.matmul(do, vf.transpose(-1, -2)) - delta))
+        p = R(p)
+        dq[:, :, r0:r1] = torch.matmul(ds, kf) * scale
+        dk += torch.matmul(ds.transpose(-1, -2), qf[:, :, r0:r1]) * scale
+        dv += torch.matmul(p.transpose(-1, -2), do)
+    return dq, dk, dv
+
+
+def two_branch_attention_bwd(q_r, k_r, v_r, kp, vp, out1, lse1, out2, lse2, alpha, dout, mask, gap,
+                             sm_scale=None, store_dtype=torch.bfloat16, emulate_rounding=False,
+                             block=128, replicate_fold=True):
+    """Op-level statement of vb_attn_bwd (include/vblade.h), every tensor in REORDERED row order:
+    the gradient w.r.t. q_r [B,H,Lq,D], k_r, v_r [B,H,Lk,D] of
+        alpha * BSA(q_r, k_r, v_r; mask)  +  storage(1 - alpha) * SDPA(q_r, pool(k_r), pool(v_r))
+    with both LSEs and alpha constants (a10; cogvideo_blocksparseattn.py:366-393): dO1 = alpha dO,
+    dO2 = storage(1-alpha) dO, each branch through block_sparse_attention_bwd's semantics with its
+    own output and LSE (out1/lse1, out2/lse2 as the forward wrote them), the pooled K/V gradients
+    folded back through simple_pooling_bwd. ``alpha`` [B,H,Lq] is any constant in [0,1] per row.
+    kp None: the main branch alone (alpha None = 1). Rows with lse = +-inf contribute nothing.
+    Lq != Lk (mask [B,H,ceil(Lq/block),ceil(Lk/block)]) and ``sm_scale`` are honoured.
+
+    ``emulate_rounding``: the same in fp64 but rounded to ``store_dtype`` exactly where the kernels
+    round (csrc/vb_attn_bwd.hip): the weighted probabilities w*P and dS of each branch (the MFMA
+    operands), and the three results (dq of both branches, dk/dv after the pool fold, summed in the
+    accumulator and rounded once). ``replicate_fold=False`` drops the replicate-padding term of the
+    mean-pool adjoint: a deliberately wrong reference for testing the error metric.
+    Returns fp32 (dq_r, dk_r, dv_r)."""
+    D = q_r.shape[-1]
+    Lk = k_r.shape[2]
+    scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(D)
+    rd = store_dtype if emulate_rounding else None
+    w1 = torch.ones(q_r.shape[:3]) if alpha is None else alpha.float()
+    dq, dk, dv = _branch_bwd(q_r, k_r, v_r, out1, lse1, dout, w1, mask, scale, block, rd)
+    if kp is not None:
+        w2 = rnd(1.0 - w1, store_dtype)
+        dq2, dkp, dvp = _branch_bwd(q_r, kp, vp, out2, lse2, dout, w2, None, scale, block, rd)
+        dq = dq + dq2
+        for g, gp in ((dk, dkp), (dv, dvp)):
+            e = (gp / gap).repeat_interleave(gap, dim=2)
+            g += e[:, :, :Lk]
+            if replicate_fold and e.shape[2] > Lk:
+                g[:, :, Lk - 1] += e[:, :, Lk:].sum(2)
+    if emulate_rounding:
+        dq, dk, dv = (t.to(store_dtype) for t in (dq, dk, dv))
+    return dq.float(), dk.float(), dv.float()
+
+
+def per_row_error(g: torch.Tensor, ref: torch.Tensor):
+    """Checker metric that a single wrong row cannot hide in: err[b,h,r] = ||g[b,h,r] - ref[b,h,r]||
+    / max(||ref[b,h,r]||, rms), rms = the root-mean-square row norm of ``ref`` (rows whose reference
+    is near zero are judged at the tensor's scale). Returns (worst error, (b, h, r) of that row)."""
+    g, ref = g.detach().double().cpu(), ref.detach().double().cpu()
+    rn = ref.norm(dim=-1)
+    rms = rn.pow(2).mean().sqrt().clamp_min(1e-300)
+    err = (g - ref).norm(dim=-1) / torch.maximum(rn, rms)
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    i = int(err.argmax())
+    return float(err.flatten()[i]), tuple(int(x) for x in np.unravel_index(i, err.shape))
+
+
+# the most a derived per-row bound may be: ~2.4x / ~3x the worst row the emulation shows (3.3-4.2e-3
+# bf16, 3.8-5.1e-4 f16 on the backward tests' shapes), so a loose emulation cannot loosen the tests
+PER_ROW_CAP = {torch.bfloat16: 1e-2, torch.float16: 1.5e-3}
+
+
+def per_row_bound(emu: torch.Tensor, ref: torch.Tensor, store_dtype) -> float:
+    """The backward tests' per-row bound for one gradient: 2x the worst per-row error of the rounding
+    emulation against the unrounded reference on the same inputs (the factor covers the spread of a
+    maximum over rows and the kernels' fp32 summation order, not kernel error), which must itself
+    stay under PER_ROW_CAP."""
+    bound = 2.0 * per_row_error(emu, ref)[0]
+    assert 0 < bound <= PER_ROW_CAP[store_dtype], (bound, PER_ROW_CAP[store_dtype])
+    return bound
+
+
 def block_mask_from_density(B, H, nbq, nbk, density, seed=3):
     """BASELINE.md §3 synthetic mask: (rand < density) | eye, at least one block per row."""
     g = torch.Generator().manual_seed(seed)

@@ -5,7 +5,8 @@ inputs and the same forward statistics (out, lse).
 Tolerance: relative Frobenius error ||g - g_ref|| / ||g_ref|| <= 2e-2 per gradient. The kernels
 feed P and dS to the MFMAs in the storage dtype (as the reference library's backward does) and
 accumulate in fp32; the oracle keeps everything in fp64 — bf16 rounding of P/dS alone gives
-errors of ~4e-3 relative.
+errors of ~4e-3 relative. The two op-level oracle tests also hold every row to the per-row bound of
+tests/test_gpu_backward_branches.py (2x the rounding emulation's worst row on the same inputs).
 """
 import math
 
@@ -43,6 +44,13 @@ def _ops():
     return ops
 
 
+def _main_branch_emulation(q, k, v, out, lse, do, mask, dtype):
+    """The oracle's storage-rounding emulation of the main-branch backward on a test's own inputs:
+    O.per_row_bound turns its worst row into the per-row bound (tests/test_gpu_backward_branches.py)."""
+    return O.two_branch_attention_bwd(q, k, v, None, None, out.cpu(), lse.cpu(), None, None, None, do, mask, 0,
+                                      store_dtype=dtype, emulate_rounding=True)
+
+
 @pytest.mark.parametrize("L,D,dtype,density", [(300, 64, torch.bfloat16, 0.5),
                                                (256, 128, torch.bfloat16, 1.0),
                                                (517, 64, torch.float16, 0.3),
@@ -62,9 +70,11 @@ def test_block_sparse_bwd_matches_oracle(L, D, dtype, density):
     dq, dk, dv = ops.attention_bwd(do.to(DEV), q.to(DEV), k.to(DEV), v.to(DEV), out, lse,
                                    block_mask=mask.to(DEV))
     rq, rk, rv = O.block_sparse_attention_bwd(q, k, v, out.cpu(), lse.cpu(), do, mask)
-    for name, g, r in (("dq", dq, rq), ("dk", dk, rk), ("dv", dv, rv)):
+    emu = _main_branch_emulation(q, k, v, out, lse, do, mask, dtype)
+    for name, g, r, e in (("dq", dq, rq, emu[0]), ("dk", dk, rk, emu[1]), ("dv", dv, rv, emu[2])):
         assert torch.isfinite(g).all(), name
         assert rel(g, r) <= TOL, (name, rel(g, r))
+        assert O.per_row_error(g, r)[0] <= O.per_row_bound(e, r, dtype), (name, O.per_row_error(g, r))
 
 
 @pytest.mark.parametrize("L,D,dtype,density", [(1000, 64, torch.bfloat16, 0.25), (1000, 128, torch.bfloat16, 0.25),
@@ -83,8 +93,10 @@ def test_default_backward_kernels_at_the_rounding_floor(L, D, dtype, density):
     dq, dk, dv = ops.attention_bwd(do.to(DEV), q.to(DEV), k.to(DEV), v.to(DEV), out, lse, block_mask=mask.to(DEV))
     rq, rk, rv = O.block_sparse_attention_bwd(q, k, v, out.cpu(), lse.cpu(), do, mask)
     tight = 4e-3 if dtype == torch.bfloat16 else 6e-4
-    for name, g, r in (("dq", dq, rq), ("dk", dk, rk), ("dv", dv, rv)):
+    emu = _main_branch_emulation(q, k, v, out, lse, do, mask, dtype)
+    for name, g, r, e in (("dq", dq, rq, emu[0]), ("dk", dk, rk, emu[1]), ("dv", dv, rv, emu[2])):
         assert rel(g, r) <= tight, (name, rel(g, r))
+        assert O.per_row_error(g, r)[0] <= O.per_row_bound(e, r, dtype), (name, O.per_row_error(g, r))
 
 
 def _lib_bits():

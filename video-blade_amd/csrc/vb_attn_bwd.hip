@@ -236,8 +236,10 @@ __global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd
     Lkey = kPooled ? p.Lpad >> ml_e : Lk;
     k0 = ml_m * (kPooled ? kRows : kBlk);
   }
-  if (k0 >= Lkey || Lq <= 0) return;
-  const int nbq = (Lq + kBlk - 1) / kBlk;
+  if (k0 >= Lkey) return;
+  // a varlen sequence with keys and no query (Lq = 0): an empty q-list, and the epilogue writes the
+  // zero dk/dv rows (as for a key block that no mask row keeps)
+  const int nbq = Lq > 0 ? (Lq + kBlk - 1) / kBlk : 0;
 
   bool nan_head = false;
   const uint8_t* mcol = nullptr;

@@ -436,8 +436,9 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
   }
   const int Lkey = kPooled ? p.Lkp : Lk;
   const int k0 = kblk * kBlk;
-  if (k0 >= Lkey || Lq <= 0) return;
-  const int nbq = (Lq + kBlk - 1) / kBlk;
+  if (k0 >= Lkey) return;
+  // Lq = 0 (a varlen sequence with keys and no query): an empty q-list; the epilogue writes zeros
+  const int nbq = Lq > 0 ? (Lq + kBlk - 1) / kBlk : 0;
 
   bool nan_head = false;
   const uint8_t* mcol = nullptr;

@@ -250,13 +250,16 @@ def _mask_u8(block_mask, Lq, Lk):
 def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_rows=None,
                   kp=None, vp=None, out2=None, lse2=None, alpha=None, gap: int = 0,
                   scale: Optional[float] = None, heavy_rows: int = 0, dk_rows: Optional[int] = None,
-                  kernel_select: int = 0, kernels_ran: Optional[list] = None):
+                  kernel_select: int = 0, kernels_ran: Optional[list] = None,
+                  workspace_bytes: Optional[list] = None):
     """vb_attn_bwd: gradients (dq, dk, dv) of the block-sparse attention, optionally of the
     adaptive two-branch form (kp/vp/out2/lse2/alpha/gap: alpha detached, pooled grads folded back
     through the mean pool). k/v hold keys in reordered order; dk/dv rows are written at
     kv_rows[g] (dk_rows = number of rows of dk/dv, default Lk). Returns bf16/fp16 tensors.
     ``kernel_select``: _lib.VB_BWD_SEL_* bits (0: the default kernels); ``kernels_ran`` (a list)
-    receives the _lib.VB_BWD_RAN_* bits of the kernels the call launched."""
+    receives the _lib.VB_BWD_RAN_* bits of the kernels the call launched; ``workspace_bytes`` (a
+    list) the size vb_attn_bwd_workspace_size reported for the call (it holds psplit copies of the
+    pooled-key partials, so tests read the pooled-key split from it)."""
     dev = _require_gpu(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2,
                        alpha)
     q, k, v, out, dout = (_aligned_bhld(t) for t in (q, k, v, out, dout))
@@ -298,6 +301,8 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
     a.kernels_ran = ctypes.pointer(ran)
     lib = _lib.load()
     nbytes = int(lib.vb_attn_bwd_workspace_size(ctypes.byref(a)))
+    if workspace_bytes is not None:
+        workspace_bytes.append(nbytes)
     ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     check(lib.vb_attn_bwd(ctypes.byref(a), _stream(dev)), "vb_attn_bwd")
