@@ -206,7 +206,14 @@ typedef struct vb_predict_args {
   int32_t* mask_rows_kept;
 } vb_predict_args;
 uint64_t vb_mask_predict_workspace_size(const vb_predict_args* args);
-int vb_mask_predict(const vb_predict_args* args, void* stream);
+int vb_mask_predict(const vb_predict_args* args, void* stream);   /* nb <= 320 (L <= 40960) */
+/* vb_mask_predict for rows of up to 1024 blocks (L <= 131072, the attention kernels' own limit).
+ * Same arguments, outputs, options and workspace (vb_mask_predict_workspace_size) as
+ * vb_mask_predict; accepts any nb in [1, 1024] and fails with VB_ERR_UNSUPPORTED past that. A second
+ * instantiation of the same score kernel whose epilogue ranks up to 16 values per lane: for
+ * nb <= 320 it writes the bits vb_mask_predict writes. The workspace holds nb*nb*64 bytes of block
+ * maxima per (b,h): 22 MB at 591 blocks (Wan 720p), 67 MB at 1024. */
+int vb_mask_predict_long(const vb_predict_args* args, void* stream);
 
 /* random_sample_tokens' index draw (cogvideo_blocksparseattn.py:45-46): the caller draws the
  * uniforms (torch.rand(B,H,1,block), q first then k, so the RNG stream is the reference's); this
@@ -216,7 +223,7 @@ int vb_sample_offsets(const float* rand_q, const float* rand_k, int rows, int n,
                       int32_t* q_off, int32_t* k_off, void* stream);
 
 /* Energy rule alone on given scores (transfer_attn_to_mask, mode="energy"):
- * po [B,H,nr,nc] contiguous storage dtype -> mask [B,H,nr,nc]. */
+ * po [B,H,nr,nc] contiguous storage dtype -> mask [B,H,nr,nc], nc <= 1024. */
 int vb_energy_mask(const void* po, int B, int H, int nr, int nc, float energy_threshold,
                    int min_keep, int max_keep, int force_tail, int dtype, uint8_t* mask,
                    unsigned long long* mask_count, void* stream);

@@ -32,6 +32,11 @@ constexpr int kPWaves = VB_PRED_WAVES;
 constexpr int kPThreads = 64 * kPWaves;
 constexpr int kMaxNb = 320;        // sampled blocks per side (L <= 40960 at block 128)
 constexpr int kEnergyRow = kMaxNb + 16;   // LDS floats per energy-rule row buffer (keys padded to 16)
+// the long instantiation (vb_mask_predict_long, vb_energy_mask past kMaxNb columns): rows of up to
+// 1024 blocks, the attention kernels' own limit (L <= 131072)
+constexpr int kMaxNbLong = 1024;
+constexpr int kEnergyRowLong = kMaxNbLong + 16;
+template <bool kLong> constexpr int kERow = kLong ? kEnergyRowLong : kEnergyRow;
 // keys per LDS tile: D=64 streams four 32-key sampled blocks per barrier (16 MFMAs per wave),
 // D=128 two (also 16 MFMAs); 16 KiB tiles in a 2-deep ring at D=64 (36.5 KiB with the row-offset
 // ring: four workgroups per CU) and a 3-deep ring at D=128 (52.5 KiB: three per CU)
@@ -289,8 +294,10 @@ __device__ __forceinline__ int energy_row_u(const float* val, uint32_t* keys, ui
   for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
   return kept;
 }
-// U = values per lane, the smallest that covers the row (ranks cost nc * U compares per lane)
-template <class T>
+// U = values per lane, the smallest that covers the row (ranks cost nc * U compares per lane).
+// kLong: rows of up to kMaxNbLong columns (U up to 16, even past 8); rows of up to kMaxNb columns
+// run the same energy_row_u<T, U> either way.
+template <class T, bool kLong = false>
 __device__ __forceinline__ int energy_row(const float* val, uint32_t* keys, uint8_t* mrow, int nc, float thr,
                           int min_keep, int max_keep, int force_cols, bool force_all) {
   switch ((nc + 63) >> 6) {
@@ -298,9 +305,22 @@ __device__ __forceinline__ int energy_row(const float* val, uint32_t* keys, uint
     case 2: return energy_row_u<T, 2>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
     case 3: return energy_row_u<T, 3>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
     case 4: return energy_row_u<T, 4>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
-    default: return energy_row_u<T, (kMaxNb + 63) / 64>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols,
-                                                           force_all);
+    default: break;
   }
+  if constexpr (kLong) {
+    switch ((nc + 63) >> 6) {
+      case 5: break;
+      case 6: return energy_row_u<T, 6>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      case 7: return energy_row_u<T, 7>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      case 8: return energy_row_u<T, 8>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      case 9: case 10: return energy_row_u<T, 10>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      case 11: case 12: return energy_row_u<T, 12>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      case 13: case 14: return energy_row_u<T, 14>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+      default: return energy_row_u<T, (kMaxNbLong + 63) / 64>(val, keys, mrow, nc, thr, min_keep, max_keep,
+                                                               force_cols, force_all);
+    }
+  }
+  return energy_row_u<T, (kMaxNb + 63) / 64>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
 }
 
 // Multi-level rank bands (transfer_attn_to_mask, Triton/cogvideo_newattn.py:154-207; vb_level_mask's
@@ -313,6 +333,27 @@ __device__ __forceinline__ void level_row_u(const float* val, uint32_t* keys, ui
   const int lane = threadIdx.x & 63;
   int rank[U];
   row_ranks<T, U>(val, keys, nc, rank);
+  if constexpr (U > (kMaxNb + 63) / 64) {
+    // long rows: bands outermost, so each band's bounds are read once, not once per value (the same
+    // result: the last band that holds the rank wins). Unrolled per value, the reads of `lv` in
+    // all the long instantiations pass the compiler's limit for keeping a kernel argument out of
+    // a private copy (scratch).
+    int l[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) l[u] = 0;
+    for (int b = 0; b < lv.n; ++b) {
+      const int s = lv.start[b], e = lv.end[b], v = lv.value[b];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (rank[u] >= s && rank[u] < e) l[u] = v;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = lane + 64 * u;
+      if (j < nc) mrow[j] = (uint8_t)((j >= nc - 2 || row >= nc - 2) ? 1 : l[u]);
+    }
+    return;
+  }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int j = lane + 64 * u;
@@ -323,7 +364,7 @@ __device__ __forceinline__ void level_row_u(const float* val, uint32_t* keys, ui
     if (j < nc) mrow[j] = (uint8_t)l;
   }
 }
-template <class T>
+template <class T, bool kLong = false>
 __device__ __forceinline__ void level_row(const float* val, uint32_t* keys, uint8_t* mrow, int nc, int row,
                                           const PredBands& lv) {
   switch ((nc + 63) >> 6) {
@@ -331,8 +372,21 @@ __device__ __forceinline__ void level_row(const float* val, uint32_t* keys, uint
     case 2: return level_row_u<T, 2>(val, keys, mrow, nc, row, lv);
     case 3: return level_row_u<T, 3>(val, keys, mrow, nc, row, lv);
     case 4: return level_row_u<T, 4>(val, keys, mrow, nc, row, lv);
-    default: return level_row_u<T, (kMaxNb + 63) / 64>(val, keys, mrow, nc, row, lv);
+    default: break;
   }
+  if constexpr (kLong) {
+    switch ((nc + 63) >> 6) {
+      case 5: break;
+      case 6: return level_row_u<T, 6>(val, keys, mrow, nc, row, lv);
+      case 7: return level_row_u<T, 7>(val, keys, mrow, nc, row, lv);
+      case 8: return level_row_u<T, 8>(val, keys, mrow, nc, row, lv);
+      case 9: case 10: return level_row_u<T, 10>(val, keys, mrow, nc, row, lv);
+      case 11: case 12: return level_row_u<T, 12>(val, keys, mrow, nc, row, lv);
+      case 13: case 14: return level_row_u<T, 14>(val, keys, mrow, nc, row, lv);
+      default: return level_row_u<T, (kMaxNbLong + 63) / 64>(val, keys, mrow, nc, row, lv);
+    }
+  }
+  return level_row_u<T, (kMaxNb + 63) / 64>(val, keys, mrow, nc, row, lv);
 }
 
 // random_sample_tokens' topk (cogvideo_blocksparseattn.py:45-46) by one wave: the indices of the
@@ -453,7 +507,9 @@ __global__ void __launch_bounds__(256) sample_rows_kernel(const PredParams p) {
   }
 }
 
-template <int D, class T, bool kEnergy>
+// kLong: the instantiation behind vb_mask_predict_long. Only the epilogue differs: the per-wave row
+// scratch holds kEnergyRowLong entries and the rank/cumsum code covers up to 16 values per lane.
+template <int D, class T, bool kEnergy, bool kLong = false>
 __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_predict_kernel(const PredParams p) {
   constexpr int KS = D / 16;
   constexpr int kRowB = D * 2;                        // bytes per key row
@@ -489,7 +545,13 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   const int nb = p.nb;
   float* mrow_s = reinterpret_cast<float*>(smem);
   uint8_t* ktile = smem + kPWaves * KQ * 32 * 4;
-  float* rowbuf = reinterpret_cast<float*>(ktile);  // [4][2][kEnergyRow], reused after the loop
+  float* rowbuf = reinterpret_cast<float*>(ktile);  // [4][2][kERow<kLong>], reused after the loop
+#if VB_PRED_GATHER
+  // the row scratch overlays the K ring and the row-offset ring behind it (36 KiB at D=64, 52 KiB at
+  // D=128); both are idle after the main loop's final vmcnt(0) and barrier
+  static_assert(kPWaves * 2 * kERow<kLong> * 4 <= kBufs * kTileBytes + 4 * kPWaves * 256,
+                "the per-wave row scratch must fit in the K-tile ring it overlays");
+#endif
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -776,8 +838,8 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   // Po[qb, j] = storage(max_r exp2(R[r][j] - m_r)) = storage(exp2(max_r (R[r][j] - m_r)))
   // (exp2 and the rounding are monotone), then the storage-dtype row normalisation; one q-block
   // after the other (the wave's row scratch is reused)
-  float* val = rowbuf + wave * 2 * (kEnergyRow);
-  uint32_t* keys = reinterpret_cast<uint32_t*>(val + kEnergyRow);
+  float* val = rowbuf + wave * 2 * (kERow<kLong>);
+  uint32_t* keys = reinterpret_cast<uint32_t*>(val + kERow<kLong>);
   auto epilogue = [&](const int qb, const uint16_t* Rq, const float* mw) __attribute__((always_inline)) {
     // this wave's R columns were stored by its own lanes: wait for them and drop any stale L1 line
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -843,11 +905,11 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
     __builtin_amdgcn_wave_barrier();
     uint8_t* mrow = p.mask + ((int64_t)bh * nb + qb) * nb;
     if (p.level) {   // the multi-level path's rank bands instead of the energy rule
-      level_row<T>(val, keys, mrow, nb, qb, p.lv);
+      level_row<T, kLong>(val, keys, mrow, nb, qb, p.lv);
       return;
     }
     const bool force_all = p.force_tail > 0 && qb >= nb - p.force_tail;
-    const int kept = energy_row<T>(val, keys, mrow, nb, p.thr, p.min_keep, p.max_keep, p.force_tail, force_all);
+    const int kept = energy_row<T, kLong>(val, keys, mrow, nb, p.thr, p.min_keep, p.max_keep, p.force_tail, force_all);
     if (p.count && lane == 0) atomicAdd(p.count, (unsigned long long)kept);
     if (p.rows_kept && lane == 0) p.rows_kept[(int64_t)bh * nb + qb] = kept;
   };
@@ -869,31 +931,38 @@ __global__ void __launch_bounds__(256) topk_offsets_kernel(const float* rq, cons
   topk_wave((blockIdx.y ? rk : rq) + (int64_t)row * n, n, keep, (blockIdx.y ? ok : oq) + (int64_t)row * keep, buf[wave]);
 }
 
+// LDS floats per row buffer of energy_mask_kernel (val and keys each; keys padded to 16)
+__host__ __device__ inline int energy_row_floats(int nc) { return nc <= kMaxNb ? kEnergyRow : ((nc + 15) & ~15); }
+static size_t energy_smem_bytes(int nc) { return (size_t)4 * 2 * energy_row_floats(nc) * 4; }
+
 template <class T>
 __global__ void __launch_bounds__(256) energy_mask_kernel(const void* po, int rows_total, int nc, float thr,
                                                           int min_keep, int max_keep, int force_tail, int nr,
                                                           uint8_t* mask, unsigned long long* count) {
-  __shared__ __attribute__((aligned(16))) float buf[4][2 * (kEnergyRow)];
+  // [4 waves][val | keys], energy_row_floats(nc) floats each (dynamic: rows of up to kMaxNb columns
+  // keep the 10.5 KiB the static buffer took)
+  extern __shared__ __attribute__((aligned(16))) float energy_buf[];
+  const int erow = energy_row_floats(nc);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= rows_total) return;
   const typename T::raw* src = reinterpret_cast<const typename T::raw*>(po) + (int64_t)row * nc;
-  float* val = buf[wave];
+  float* val = energy_buf + wave * 2 * erow;
   for (int j = lane; j < nc; j += 64) val[j] = T::to_f32(src[j]);
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_wave_barrier();
   const int i = row % nr;
   const bool force_all = force_tail > 0 && i >= nr - force_tail;
-  const int kept = energy_row<T>(val, reinterpret_cast<uint32_t*>(val + kEnergyRow), mask + (int64_t)row * nc, nc,
-                                 thr, min_keep, max_keep, force_tail, force_all);
+  const int kept = energy_row<T, true>(val, reinterpret_cast<uint32_t*>(val + erow), mask + (int64_t)row * nc, nc,
+                                       thr, min_keep, max_keep, force_tail, force_all);
   if (count && lane == 0) atomicAdd(count, (unsigned long long)kept);
 }
 
-static size_t predict_smem_bytes(int nb, int D) {
+static size_t predict_smem_bytes(int nb, int D, bool long_rows) {
   (void)nb;
   const size_t tiles = D == 64 ? (size_t)kPBufs<64> * kKeysPerTile<64> * 64 * 2
                                : (size_t)kPBufs<128> * kKeysPerTile<128> * 128 * 2;
-  const size_t scratch = (size_t)kPWaves * 2 * (kEnergyRow) * 4;
+  const size_t scratch = (size_t)kPWaves * 2 * (long_rows ? kEnergyRowLong : kEnergyRow) * 4;
   const size_t ring = VB_PRED_GATHER ? 4 * kPWaves * 256 : 0;   // gather mode: the row-offset ring
   const size_t mrow = (size_t)kPWaves * (D == 64 ? kQPW<64> : kQPW<128>) * 32 * 4;
   return mrow + (tiles + ring > scratch ? tiles + ring : scratch);
@@ -924,10 +993,10 @@ static int64_t philox_x_only_numel() {
   return n;
 }
 
-template <int D, class T>
+template <int D, class T, bool kLong>
 static int launch_predict(const PredParams& p, hipStream_t stream, hipEvent_t staged) {
-  const size_t smem = predict_smem_bytes(p.nb, D);
-  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY>;
+  const size_t smem = predict_smem_bytes(p.nb, D, kLong);
+  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY, kLong>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)smem) != hipSuccess)
     return fail(VB_ERR_LAUNCH, "mask_predict: cannot reserve LDS");
@@ -941,7 +1010,7 @@ static int launch_predict(const PredParams& p, hipStream_t stream, hipEvent_t st
   if (int rc = check_launch("mask_predict_kernel")) return rc;
   if (VB_PRED_SPLIT_ENERGY && p.mask) {
     const int rows = p.B * p.H * p.nb;
-    hipLaunchKernelGGL(energy_mask_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, p.po, rows, p.nb, p.thr,
+    hipLaunchKernelGGL(energy_mask_kernel<T>, dim3((rows + 3) / 4), dim3(256), energy_smem_bytes(p.nb), stream, p.po, rows, p.nb, p.thr,
                        p.min_keep, p.max_keep, p.force_tail, p.nb, p.mask, p.count);
     return check_launch("energy_mask_kernel");
   }
@@ -967,27 +1036,36 @@ extern "C" uint64_t vb_mask_predict_workspace_size(const vb_predict_args* a) {
   return vb::predict_ws_bytes(a->B, a->H, a->L, a->D);
 }
 
-extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) {
+// vb_mask_predict and vb_mask_predict_long: one validation and parameter set-up, `fn` names the entry
+// in the messages, kLong selects the row limit and the kernel instantiation.
+template <bool kLong>
+static int mask_predict_entry(const vb_predict_args* a, void* stream) {
   using namespace vb;
+  const std::string fn = kLong ? "vb_mask_predict_long: " : "vb_mask_predict: ";
   if (!a || !a->q || !a->k || !a->q_off || !a->k_off || !a->po)
-    return fail(VB_ERR_INVALID, "vb_mask_predict: null argument");
-  if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, "vb_mask_predict: bad sizes");
+    return fail(VB_ERR_INVALID, fn + "null argument");
+  if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, fn + "bad sizes");
   if (a->block != 128 || a->num_keep != 32)
-    return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: block must be 128 and num_keep 32 (the reference's values)");
+    return fail(VB_ERR_UNSUPPORTED, fn + "block must be 128 and num_keep 32 (the reference's values)");
   const int nb = (a->L + a->block - 1) / a->block;
-  if (nb > kMaxNb) return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: sequence too long");
-  if (a->L > 65535) return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: L must be < 65536");
-  if (a->min_keep < 1 || a->max_keep < 1) return fail(VB_ERR_INVALID, "vb_mask_predict: keep counts must be >= 1");
-  if (a->D != 64 && a->D != 128) return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: head_dim must be 64 or 128");
+  if (nb > (kLong ? kMaxNbLong : kMaxNb)) return fail(VB_ERR_UNSUPPORTED, fn + "sequence too long");
+  // The short entry's L < 65536 guard came with the packed sort keys. Audit of every 16-bit quantity
+  // on this path: the sort key's low 16 bits hold 0xFFFF - (block index <= 1023) and its high 16 the
+  // score's storage bits; R holds storage bits; the buffer descriptors' 16-bit field is the (zero)
+  // stride. Token positions are int32 throughout (sampled_row, the int32 byte-offset table, the
+  // descriptors' byte counts, checked < 2^31 below), so the long entry has no such guard.
+  if (!kLong && a->L > 65535) return fail(VB_ERR_UNSUPPORTED, fn + "L must be < 65536");
+  if (a->min_keep < 1 || a->max_keep < 1) return fail(VB_ERR_INVALID, fn + "keep counts must be >= 1");
+  if (a->D != 64 && a->D != 128) return fail(VB_ERR_UNSUPPORTED, fn + "head_dim must be 64 or 128");
   const uint64_t ws = predict_ws_bytes(a->B, a->H, a->L, a->D);
   if (!a->workspace || a->workspace_bytes < ws || (reinterpret_cast<uintptr_t>(a->workspace) & 15))
-    return fail(VB_ERR_INVALID, "vb_mask_predict: workspace missing or smaller than vb_mask_predict_workspace_size()");
+    return fail(VB_ERR_INVALID, fn + "workspace missing or smaller than vb_mask_predict_workspace_size()");
   const uint64_t rows_b = predict_rows_bytes(a->B, a->H, a->L, a->D);
-  if (rows_b / a->B / a->H >= (uint64_t(1) << 31)) return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: sampled stream too large");
+  if (rows_b / a->B / a->H >= (uint64_t(1) << 31)) return fail(VB_ERR_UNSUPPORTED, fn + "sampled stream too large");
   if ((int64_t)(a->L - 1) * a->k_stride[2] * 2 + 2 * a->D >= (int64_t(1) << 31))
-    return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: a k (b,h) slice spans >= 2 GiB");
+    return fail(VB_ERR_UNSUPPORTED, fn + "a k (b,h) slice spans >= 2 GiB");
   for (int i = 0; i < 3; ++i)
-    if ((a->q_stride[i] | a->k_stride[i]) & 7) return fail(VB_ERR_INVALID, "vb_mask_predict: strides must be multiples of 8");
+    if ((a->q_stride[i] | a->k_stride[i]) & 7) return fail(VB_ERR_INVALID, fn + "strides must be multiples of 8");
   PredParams p{};
   p.q = a->q; p.k = a->k;
   for (int i = 0; i < 3; ++i) { p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; }
@@ -1000,27 +1078,27 @@ extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) {
   p.po = a->po; p.mask = a->mask; p.count = a->mask_count;
   // the kept counts come from the energy rule of the fused epilogue: refused where it does not run
   if (a->mask_rows_kept && (a->mask_level || !a->mask || VB_PRED_SPLIT_ENERGY))
-    return fail(VB_ERR_INVALID, "vb_mask_predict: mask_rows_kept needs the energy mask (mask set, mask_level 0)");
+    return fail(VB_ERR_INVALID, fn + "mask_rows_kept needs the energy mask (mask set, mask_level 0)");
   p.rows_kept = a->mask_rows_kept;
   p.q_s = nullptr;
   p.k_s = reinterpret_cast<uint8_t*>(a->workspace);
   p.rbuf = reinterpret_cast<uint16_t*>(p.k_s + rows_b);
   if ((a->rand_q == nullptr) != (a->rand_k == nullptr))
-    return fail(VB_ERR_INVALID, "vb_mask_predict: give both rand_q and rand_k or neither");
+    return fail(VB_ERR_INVALID, fn + "give both rand_q and rand_k or neither");
   p.rand_q = a->rand_q; p.rand_k = a->rand_k;
   if (a->level_bands < 0 || a->level_bands > 8 ||
       (a->level_bands > 0 && (!a->level_band_value || !a->level_band_start || !a->level_band_end)))
-    return fail(VB_ERR_INVALID, "vb_mask_predict: 0..8 level bands with value/start/end arrays");
+    return fail(VB_ERR_INVALID, fn + "0..8 level bands with value/start/end arrays");
   if (a->mask_level) {
-    if (!a->mask) return fail(VB_ERR_INVALID, "vb_mask_predict: mask_level needs a mask output");
+    if (!a->mask) return fail(VB_ERR_INVALID, fn + "mask_level needs a mask output");
     if (VB_PRED_SPLIT_ENERGY)   // that diagnostic build's epilogue writes the energy mask only
-      return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: mask_level needs the fused epilogue (VB_PRED_SPLIT_ENERGY=0)");
+      return fail(VB_ERR_UNSUPPORTED, fn + "mask_level needs the fused epilogue (VB_PRED_SPLIT_ENERGY=0)");
     p.level = 1;
     p.lv.n = a->level_bands;
     for (int i = 0; i < a->level_bands; ++i) {
       const int val = a->level_band_value[i];
       if (val != 0 && val != 1 && val != 2 && val != 4 && val != 8)
-        return fail(VB_ERR_INVALID, "vb_mask_predict: band values must be 0, 1, 2, 4 or 8");
+        return fail(VB_ERR_INVALID, fn + "band values must be 0, 1, 2, 4 or 8");
       // max(0, int(nb * start)), min(nb, int(nb * end)) in double, as vb_level_mask
       const int ia = (int)((double)nb * a->level_band_start[i]), ib = (int)((double)nb * a->level_band_end[i]);
       p.lv.value[i] = val;
@@ -1029,22 +1107,22 @@ extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) {
     }
   }
   if (a->philox) {
-    if (a->rand_q || a->rand_k) return fail(VB_ERR_INVALID, "vb_mask_predict: philox and rand_q/rand_k are exclusive");
+    if (a->rand_q || a->rand_k) return fail(VB_ERR_INVALID, fn + "philox and rand_q/rand_k are exclusive");
     // torch.rand's grid-stride launch gives element i the x value of thread i only while every
     // element has a thread of its own: numel <= CUs * max threads per CU of THIS device (524288 on
     // an unpartitioned MI355X; fewer in a CPX partition)
     const int64_t one_pass = philox_x_only_numel();
-    if (one_pass <= 0) return fail(VB_ERR_LAUNCH, "vb_mask_predict: cannot query the device's CU count");
+    if (one_pass <= 0) return fail(VB_ERR_LAUNCH, fn + "cannot query the device's CU count");
     if ((int64_t)a->B * a->H * a->block > one_pass)
-      return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: philox draws need B*H*block <= " + std::to_string(one_pass) +
+      return fail(VB_ERR_UNSUPPORTED, fn + "philox draws need B*H*block <= " + std::to_string(one_pass) +
                                           " (CUs x max threads per CU of this device)");
     p.philox = 1; p.philox_seed = a->philox_seed; p.philox_offset = a->philox_offset;
   }
   if (a->pool_kp) {   // the pooled K/V pass rides in the score kernel's launch
     if (!a->pool_v || !a->pool_vp || a->pool_gap <= 0 || ((a->pool_k_r == nullptr) != (a->pool_v_r == nullptr)))
-      return fail(VB_ERR_INVALID, "vb_mask_predict: pool_v, pool_vp, pool_gap > 0 and both or neither of pool_k_r/pool_v_r");
+      return fail(VB_ERR_INVALID, fn + "pool_v, pool_vp, pool_gap > 0 and both or neither of pool_k_r/pool_v_r");
     for (int i = 0; i < 3; ++i)
-      if (a->pool_v_stride[i] & 7) return fail(VB_ERR_INVALID, "vb_mask_predict: pool_v strides must be multiples of 8");
+      if (a->pool_v_stride[i] & 7) return fail(VB_ERR_INVALID, fn + "pool_v strides must be multiples of 8");
     PoolTask& t = p.pool;
     t.k = reinterpret_cast<const uint8_t*>(a->k); t.v = reinterpret_cast<const uint8_t*>(a->pool_v);
     for (int i = 0; i < 3; ++i) { t.ks[i] = a->k_stride[i]; t.vs[i] = a->pool_v_stride[i]; }
@@ -1059,13 +1137,13 @@ extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) {
     p.n_pool = (n + 7) / 8 * 8;   // keeps blockIdx % 8 of the score workgroups (their XCD)
   }
   if (a->pyr_k) {   // the KV pyramid pass rides in the score kernel's launch
-    if (a->pool_kp) return fail(VB_ERR_INVALID, "vb_mask_predict: pool_* and pyr_* are exclusive");
-    if (!a->pyr_v || !a->pool_v) return fail(VB_ERR_INVALID, "vb_mask_predict: pyr_k needs pyr_v and pool_v");
+    if (a->pool_kp) return fail(VB_ERR_INVALID, fn + "pool_* and pyr_* are exclusive");
+    if (!a->pyr_v || !a->pool_v) return fail(VB_ERR_INVALID, fn + "pyr_k needs pyr_v and pool_v");
     for (int i = 0; i < 3; ++i)
-      if (a->pool_v_stride[i] & 7) return fail(VB_ERR_INVALID, "vb_mask_predict: pool_v strides must be multiples of 8");
+      if (a->pool_v_stride[i] & 7) return fail(VB_ERR_INVALID, fn + "pool_v strides must be multiples of 8");
     if (((reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->pool_v) |
           reinterpret_cast<uintptr_t>(a->pyr_k) | reinterpret_cast<uintptr_t>(a->pyr_v)) & 15) != 0)
-      return fail(VB_ERR_INVALID, "vb_mask_predict: pyramid tensors must be 16-byte aligned");
+      return fail(VB_ERR_INVALID, fn + "pyramid tensors must be 16-byte aligned");
     PyrTask& t = p.pyr;
     t.k = reinterpret_cast<const uint8_t*>(a->k); t.v = reinterpret_cast<const uint8_t*>(a->pool_v);
     for (int i = 0; i < 3; ++i) { t.ks[i] = a->k_stride[i]; t.vs[i] = a->pool_v_stride[i]; }
@@ -1084,15 +1162,21 @@ extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipEvent_t ev = reinterpret_cast<hipEvent_t>(a->staged_event);
   if (a->dtype == VB_DTYPE_BF16) {
-    if (a->D == 64) return launch_predict<64, BF16>(p, s, ev);
-    if (a->D == 128) return launch_predict<128, BF16>(p, s, ev);
+    if (a->D == 64) return launch_predict<64, BF16, kLong>(p, s, ev);
+    if (a->D == 128) return launch_predict<128, BF16, kLong>(p, s, ev);
   } else if (a->dtype == VB_DTYPE_F16) {
-    if (a->D == 64) return launch_predict<64, F16>(p, s, ev);
-    if (a->D == 128) return launch_predict<128, F16>(p, s, ev);
+    if (a->D == 64) return launch_predict<64, F16, kLong>(p, s, ev);
+    if (a->D == 128) return launch_predict<128, F16, kLong>(p, s, ev);
   } else {
-    return fail(VB_ERR_INVALID, "vb_mask_predict: unknown dtype");
+    return fail(VB_ERR_INVALID, fn + "unknown dtype");
   }
-  return fail(VB_ERR_UNSUPPORTED, "vb_mask_predict: head_dim must be 64 or 128");
+  return fail(VB_ERR_UNSUPPORTED, fn + "head_dim must be 64 or 128");
+}
+
+extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) { return mask_predict_entry<false>(a, stream); }
+
+extern "C" int vb_mask_predict_long(const vb_predict_args* a, void* stream) {
+  return mask_predict_entry<true>(a, stream);
 }
 
 extern "C" int vb_energy_mask(const void* po, int B, int H, int nr, int nc, float energy_threshold, int min_keep,
@@ -1101,16 +1185,16 @@ extern "C" int vb_energy_mask(const void* po, int B, int H, int nr, int nc, floa
   using namespace vb;
   if (!po || !mask) return fail(VB_ERR_INVALID, "vb_energy_mask: null argument");
   if (B <= 0 || H <= 0 || nr <= 0 || nc <= 0) return fail(VB_ERR_INVALID, "vb_energy_mask: bad sizes");
-  if (nc > kMaxNb) return fail(VB_ERR_UNSUPPORTED, "vb_energy_mask: too many columns");
+  if (nc > kMaxNbLong) return fail(VB_ERR_UNSUPPORTED, "vb_energy_mask: too many columns");
   if (min_keep < 1 || max_keep < 1) return fail(VB_ERR_INVALID, "vb_energy_mask: keep counts must be >= 1");
   const int rows = B * H * nr;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((rows + 3) / 4);
   if (dtype == VB_DTYPE_BF16)
-    hipLaunchKernelGGL(energy_mask_kernel<BF16>, grid, dim3(256), 0, s, po, rows, nc, energy_threshold, min_keep,
+    hipLaunchKernelGGL(energy_mask_kernel<BF16>, grid, dim3(256), energy_smem_bytes(nc), s, po, rows, nc, energy_threshold, min_keep,
                        max_keep, force_tail, nr, mask, mask_count);
   else if (dtype == VB_DTYPE_F16)
-    hipLaunchKernelGGL(energy_mask_kernel<F16>, grid, dim3(256), 0, s, po, rows, nc, energy_threshold, min_keep,
+    hipLaunchKernelGGL(energy_mask_kernel<F16>, grid, dim3(256), energy_smem_bytes(nc), s, po, rows, nc, energy_threshold, min_keep,
                        max_keep, force_tail, nr, mask, mask_count);
   else
     return fail(VB_ERR_INVALID, "vb_energy_mask: unknown dtype");

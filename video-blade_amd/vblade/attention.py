@@ -265,7 +265,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                     energy_threshold=self.energy_threshold, min_keep=lo,
                                     max_keep=hi, force_tail=self.force_tail, mask_count=count,
                                     staged_event=staged_event, rand=rand, philox=philox,
-                                    pool=pool, rows_kept=rows_kept)
+                                    pool=pool, rows_kept=rows_kept, long_rows=nb > ops.MAX_BLOCKS)
         return po, mask
 
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *,

@@ -62,12 +62,13 @@ def predict_level_mask(q, k, *, rows=None, mask_ratios=None, q_off=None, k_off=N
         q_off, k_off = draw_sample_offsets_qk(B, H, q.device, BLOCK, 32)
     # the rank-band level mask comes out of the score kernel's epilogue (vb_predict_args.mask_level;
     # ops.level_mask is the stand-alone form of the same rule)
+    long_rows = (L + BLOCK - 1) // BLOCK > ops.MAX_BLOCKS   # past vb_mask_predict's rows: the long entry
     if not FUSED_LEVEL_MASK:
         po, _ = ops.mask_predict(q, k, q_off, k_off, rows=rows, want_mask=False, rand=rand, philox=philox,
-                                 pyr=pyr)
+                                 pyr=pyr, long_rows=long_rows)
         return po, ops.level_mask(po, mask_ratios)
     return ops.mask_predict(q, k, q_off, k_off, rows=rows, rand=rand, philox=philox, pyr=pyr,
-                            level=MASK_RATIOS if mask_ratios is None else mask_ratios)
+                            level=MASK_RATIOS if mask_ratios is None else mask_ratios, long_rows=long_rows)
 
 
 def adaptive_block_sparse_attn(q, k, v, *, rows=None, mask_ratios=None, ref_tail=True,

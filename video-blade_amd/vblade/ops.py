@@ -17,6 +17,8 @@ from . import _lib
 from ._lib import AttnArgs, BwdArgs, MlAttnArgs, MlBwdArgs, PredictArgs, check
 
 BLOCK = 128
+MAX_BLOCKS = 320         # vb_mask_predict's rows (L <= 40960)
+MAX_BLOCKS_LONG = 1024   # vb_mask_predict_long's, the attention kernels' own limit (L <= 131072)
 
 
 def _dtype_code(t: torch.Tensor) -> int:
@@ -357,7 +359,7 @@ def block_sparse_attn_bwd(dout, q_unpad, k_unpad, v_unpad, out_unpad, softmax_ls
 def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.95, min_keep=1,
                  max_keep=1, force_tail=0, scale=None, mask_count=None, want_mask=True,
                  staged_event=None, rand=None, philox=None, pool=None, pyr=None, level=None,
-                 rows_kept=None):
+                 rows_kept=None, long_rows=False):
     """vb_mask_predict. q,k [B,H,L,D]; q_off/k_off int32 [B,H,32]. Returns (po, mask) with
     po [B,H,nb,nb] in q.dtype and mask uint8 [B,H,nb,nb] (None with want_mask=False: the scores
     only, no energy rule). ``staged_event`` (a torch.cuda.Event) is recorded once the sampled
@@ -374,13 +376,15 @@ def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.
     run the same way; ``outs`` = kv_pyramid_outputs(k). Excludes ``pool``.
     ``level=mask_ratios``: the returned mask is the multi-level rank-band mask (level_mask's rule
     on the scores, computed by the score kernel's epilogue) instead of the energy mask.
-    ``rows_kept``: int32 [B,H,nb] receiving the energy rule's kept-block count per mask row."""
+    ``rows_kept``: int32 [B,H,nb] receiving the energy rule's kept-block count per mask row.
+    ``long_rows``: call vb_mask_predict_long (up to MAX_BLOCKS_LONG = 1024 blocks, L <= 131072; the
+    same outputs) instead of vb_mask_predict (up to MAX_BLOCKS = 320 blocks, L <= 40960)."""
     try:
         return _mask_predict(q, k, q_off, k_off, rows=rows, energy_threshold=energy_threshold,
                              min_keep=min_keep, max_keep=max_keep, force_tail=force_tail, scale=scale,
                              mask_count=mask_count, want_mask=want_mask, staged_event=staged_event,
                              rand=rand, philox=philox, pool=pool, pyr=pyr, level=level,
-                             rows_kept=rows_kept)
+                             rows_kept=rows_kept, long_rows=long_rows)
     except Exception as e:
         # the claimed draws go back to the generator only when nothing was launched: a Python-side
         # error (validation, or a host-side VBladeError such as the library failing to load, code
@@ -395,7 +399,8 @@ def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.
 
 
 def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_keep, force_tail,
-                  scale, mask_count, want_mask, staged_event, rand, philox, pool, pyr, level, rows_kept):
+                  scale, mask_count, want_mask, staged_event, rand, philox, pool, pyr, level, rows_kept,
+                  long_rows=False):
     if k.shape != q.shape:
         raise ValueError(f"mask_predict: k and v must have q's shape {tuple(q.shape)}, "
                          f"got k {tuple(k.shape)}")
@@ -474,7 +479,10 @@ def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_k
             raise ValueError("mask_predict: rows_kept must be contiguous int32 [B,H,nb]")
         _check_dev("mask_predict: rows_kept", rows_kept, dev)
         a.mask_rows_kept = rows_kept.data_ptr()
-    check(lib.vb_mask_predict(ctypes.byref(a), _stream(dev)), "vb_mask_predict")
+    if long_rows:
+        check(lib.vb_mask_predict_long(ctypes.byref(a), _stream(dev)), "vb_mask_predict_long")
+    else:
+        check(lib.vb_mask_predict(ctypes.byref(a), _stream(dev)), "vb_mask_predict")
     return po, mask
 
 
