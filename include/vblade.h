@@ -34,7 +34,8 @@ extern "C" {
 enum vb_status {
   VB_OK = 0,
   VB_ERR_INVALID = -1,     /* bad argument / shape */
-  VB_ERR_UNSUPPORTED = -2, /* valid for the reference op but not implemented (dropout, causal, streaming, head dim) */
+  VB_ERR_UNSUPPORTED = -2, /* valid for the reference op but not implemented (dropout, causal, streaming, head dim,
+                              a predictor num_keep other than 16, 32 or 64) */
   VB_ERR_LAUNCH = -3       /* the HIP launch failed */
 };
 
@@ -146,7 +147,11 @@ typedef struct vb_predict_args {
   const int32_t* rows;     /* [L] reordered -> caller row, or NULL */
   int32_t* q_off;          /* [B,H,num_keep] int32 in [0,block): input, or output with rand_q/rand_k */
   int32_t* k_off;
-  int B, H, L, D, block, num_keep;
+  int B, H, L, D, block, num_keep; /* block = 128. num_keep = 16, 32 or 64 sampled tokens per block (the
+                              reference's default is 32; 16 does a quarter of the score work, 64 four
+                              times), otherwise VB_ERR_UNSUPPORTED before any launch. The sampled streams
+                              have nb*num_keep rows: row j*num_keep + t of (b,h) is reordered position
+                              min(j*block + off[b,h,t], L-1). */
   float scale;             /* <= 0 -> D^-1/2 */
   float energy_threshold;
   int min_keep, max_keep, force_tail;
@@ -155,7 +160,8 @@ typedef struct vb_predict_args {
   unsigned long long* mask_count; /* nullable */
   int dtype;
   void* workspace;         /* device, 16-byte aligned, >= vb_mask_predict_workspace_size(args) bytes:
-                              the sampled k rows staged contiguously and the per-row block maxima */
+                              the sampled k rows' offsets and the per-row block maxima,
+                              B*H*(nb*num_keep*4 + nb*nb*num_keep*2) bytes; smaller: VB_ERR_INVALID */
   uint64_t workspace_bytes;
   void* staged_event;      /* nullable hipEvent_t, recorded on `stream` once the sampled rows are
                               staged (before the score kernel): independent work on another stream
@@ -211,8 +217,11 @@ int vb_mask_predict(const vb_predict_args* args, void* stream);   /* nb <= 320 (
  * Same arguments, outputs, options and workspace (vb_mask_predict_workspace_size) as
  * vb_mask_predict; accepts any nb in [1, 1024] and fails with VB_ERR_UNSUPPORTED past that. A second
  * instantiation of the same score kernel whose epilogue ranks up to 16 values per lane: for
- * nb <= 320 it writes the bits vb_mask_predict writes. The workspace holds nb*nb*64 bytes of block
- * maxima per (b,h): 22 MB at 591 blocks (Wan 720p), 67 MB at 1024. */
+ * nb <= 320 it writes the bits vb_mask_predict writes (num_keep 16 and 64 run this instantiation
+ * from either entry; each entry keeps its own nb limit). Workspace per (b,h):
+ * nb*num_keep*4 + nb*nb*num_keep*2 bytes, nearly all of it the block maxima: at num_keep 32, 22 MB
+ * at 591 blocks (Wan 720p) and 67 MB at 1024; at 1024 blocks 34 MB with num_keep 16 and 134 MB
+ * with num_keep 64. */
 int vb_mask_predict_long(const vb_predict_args* args, void* stream);
 
 /* random_sample_tokens' index draw (cogvideo_blocksparseattn.py:45-46): the caller draws the

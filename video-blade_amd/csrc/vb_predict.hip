@@ -7,7 +7,8 @@
 //   * the Triton pooled-score kernel (TrainRelated/attn_pooling_kernel.py:17-255): per sampled row
 //     the max logit of every 32-key sampled block (MFMA 32x32x16, query on the lane), rounded to the
 //     storage dtype (R), the running fp32 row max m, then Po[i,j] = max_rows exp2(R - m) and the
-//     storage-dtype row normalisation;
+//     storage-dtype row normalisation; the kernel's tile size is num_keep, the sampled tokens per
+//     block: 32 by default, 16 and 64 as further instantiations (mask_predict_kernel's kKeep);
 //   * transfer_attn_to_mask(mode="energy") (:177-249; wanx_blocksparseattn.py:162-233): stable
 //     descending rank, fp32-accumulated cumsum rounded to the storage dtype per prefix, the first
 //     crossing of storage(total * thr), clamp to [min_keep, max_keep], forced tail rows/cols.
@@ -107,8 +108,8 @@ struct PredBands {
 struct PredParams {
   const void* q; const void* k;
   int64_t qs[3], ks[3];
-  uint8_t* q_s; uint8_t* k_s;   // sampled k rows [B,H,nb*32,D] contiguous (workspace); q_s unused
-  uint16_t* rbuf;               // R [B,H,nb(q-block),nb(key block),32 rows] storage bits (workspace)
+  uint8_t* q_s; uint8_t* k_s;   // sampled k rows [B,H,nb*keep,D] contiguous (workspace); q_s unused
+  uint16_t* rbuf;               // R [B,H,nb(q-block),nb(key block),keep rows] storage bits (workspace)
   const int32_t* rows;
   int32_t* q_off; int32_t* k_off;   // inputs, or outputs when rand_q/rand_k are given
   const float* rand_q; const float* rand_k;   // [B,H,block] uniforms (nullable): offsets drawn here
@@ -446,52 +447,54 @@ __device__ __forceinline__ void topk_wave_lds(int n, int keep, int32_t* dst, con
   }
 }
 
-// Sampled rows of k, gathered once into contiguous [B,H,nb*32,D] (the q fragments are gathered by the
-// predictor's prologue directly, one row per lane):
-// row j*32 + t of (b,h) = reordered position min(j*block + off[b,h,t], L-1) (replicate padding),
+// Sampled rows of k, gathered once into contiguous [B,H,nb*keep,D] (the q fragments are gathered by
+// the predictor's prologue directly, one row per lane); keep = kKeep sampled tokens per block:
+// row j*keep + t of (b,h) = reordered position min(j*block + off[b,h,t], L-1) (replicate padding),
 // read at the caller's row rows[pos]. The predictor then streams K by plain LDS-DMA.
 // grid (row chunks, B*H). With rand_q/rand_k the offsets are drawn here first (topk_wave: one launch
 // instead of two) and the first chunk of every (b,h) writes them out for the score kernel.
-template <class T>
+template <class T, int kKeep = 32>
 __global__ void __launch_bounds__(256) sample_rows_kernel(const PredParams p) {
   __shared__ alignas(16) float sv[2][256];
-  __shared__ int32_t koff_s[32];
+  __shared__ int32_t koff_s[kKeep];
   const int bh = blockIdx.y;
   const int wave = threadIdx.x >> 6;
-  const int32_t* koff = p.k_off + (int64_t)bh * 32;
+  const int32_t* koff = p.k_off + (int64_t)bh * kKeep;
   if (p.philox) {   // the two torch.rand draws generated here: q at offset, k at offset + 4
     if (wave == 0) {
       philox_draw_wave(p.philox_seed, p.philox_offset + 4, (long long)bh * p.block, p.block, sv[0]);
-      topk_wave_lds(p.block, 32, koff_s, sv[0]);
+      topk_wave_lds(p.block, kKeep, koff_s, sv[0]);
     }
     if (blockIdx.x == 0 && wave == 1) {
       philox_draw_wave(p.philox_seed, p.philox_offset, (long long)bh * p.block, p.block, sv[1]);
-      topk_wave_lds(p.block, 32, p.q_off + (int64_t)bh * 32, sv[1]);
+      topk_wave_lds(p.block, kKeep, p.q_off + (int64_t)bh * kKeep, sv[1]);
     }
     __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x < 32) p.k_off[(int64_t)bh * 32 + threadIdx.x] = koff_s[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x < kKeep) p.k_off[(int64_t)bh * kKeep + threadIdx.x] = koff_s[threadIdx.x];
     koff = koff_s;
   } else if (p.rand_k) {
-    if (wave == 0) topk_wave(p.rand_k + (int64_t)bh * p.block, p.block, 32, koff_s, sv[0]);
+    if (wave == 0) topk_wave(p.rand_k + (int64_t)bh * p.block, p.block, kKeep, koff_s, sv[0]);
     if (blockIdx.x == 0 && wave == 1)
-      topk_wave(p.rand_q + (int64_t)bh * p.block, p.block, 32, p.q_off + (int64_t)bh * 32, sv[1]);
+      topk_wave(p.rand_q + (int64_t)bh * p.block, p.block, kKeep, p.q_off + (int64_t)bh * kKeep, sv[1]);
     __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x < 32) p.k_off[(int64_t)bh * 32 + threadIdx.x] = koff_s[threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x < kKeep) p.k_off[(int64_t)bh * kKeep + threadIdx.x] = koff_s[threadIdx.x];
     koff = koff_s;
   }
   // one thread per sampled row: the two index loads once, then D/8 independent 16-byte copies
   const int jt = blockIdx.x * blockDim.x + threadIdx.x;
-  if (jt >= p.nb * 32) return;
+  if (jt >= p.nb * kKeep) return;
   const int b = bh / p.H, h = bh % p.H;
-  int pos = min((jt >> 5) * p.block + koff[jt & 31], p.L - 1);
+  constexpr int kKeepLog2 = kKeep == 16 ? 4 : kKeep == 32 ? 5 : 6;
+  static_assert(kKeep == 1 << kKeepLog2, "sampling densities: 16, 32 or 64 tokens per block");
+  int pos = min((jt >> kKeepLog2) * p.block + koff[jt & (kKeep - 1)], p.L - 1);
   if (p.rows) pos = p.rows[pos];
   if (VB_PRED_GATHER) {   // the score kernel gathers the rows: only their byte offsets in the (b,h) slice
-    reinterpret_cast<int32_t*>(p.k_s)[(int64_t)bh * p.nb * 32 + jt] = (int32_t)((int64_t)pos * p.ks[2] * 2);
+    reinterpret_cast<int32_t*>(p.k_s)[(int64_t)bh * p.nb * kKeep + jt] = (int32_t)((int64_t)pos * p.ks[2] * 2);
     return;
   }
   const u32x4* src = reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(p.k) +
                                                     2 * (b * p.ks[0] + h * p.ks[1] + (int64_t)pos * p.ks[2]));
-  u32x4* dst = reinterpret_cast<u32x4*>(p.k_s + ((int64_t)bh * p.nb * 32 + jt) * p.D * 2);
+  u32x4* dst = reinterpret_cast<u32x4*>(p.k_s + ((int64_t)bh * p.nb * kKeep + jt) * p.D * 2);
   if (p.D == 64) {
     u32x4 x[8];
 #pragma unroll
@@ -509,8 +512,24 @@ __global__ void __launch_bounds__(256) sample_rows_kernel(const PredParams p) {
 
 // kLong: the instantiation behind vb_mask_predict_long. Only the epilogue differs: the per-wave row
 // scratch holds kEnergyRowLong entries and the rank/cumsum code covers up to 16 values per lane.
-template <int D, class T, bool kEnergy, bool kLong = false>
+//
+// kKeep: sampled tokens per 128-token block (16, 32 or 64; the reference's num_keep). The sampled
+// streams have nb*kKeep rows and the score loop runs over them in the same 32x32 MFMA tiles; what
+// changes is which tile rows and lanes belong to one (q-block, key block) pair:
+//   * 32: a wave's 32 query lanes are one q-block, a 32-key tile one key block.
+//   * 64: a q-block is two 32-row groups (two neighbouring waves), a key block two 32-key tiles. The
+//     block's row maximum is the maximum over both tiles (every lane ends up holding it); R is
+//     [q-block][key block][64 rows], each wave storing its 32 rows; the even wave of a pair runs the
+//     epilogue over both groups' rows and row maxima.
+//   * 16: a 32x32 tile is two q-blocks (lanes 0-15 / 16-31 of each half) by two key blocks
+//     (accumulator registers 0-7 / 8-15). One permlane32_swap of the two 8-register maxima gives
+//     lanes 0-31 the first key block's row maximum and lanes 32-63 the second's; R is
+//     [q-block][key block][16 rows]; a wave runs the epilogue of its two q-blocks in turn.
+// The wave's unit of work is therefore a 32-row *group* of the sampled q stream (`qbs`, `ng` of them).
+template <int D, class T, bool kEnergy, bool kLong = false, int kKeep = 32>
 __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_predict_kernel(const PredParams p) {
+  static_assert(kKeep == 16 || kKeep == 32 || kKeep == 64, "sampling densities: 16, 32 or 64 tokens per block");
+  static_assert(kKeep == 32 || (kQPW<D> == 1 && VB_PRED_GATHER), "densities 16 and 64: one group per wave, gather mode");
   constexpr int KS = D / 16;
   constexpr int kRowB = D * 2;                        // bytes per key row
   constexpr int kKT = kKeysPerTile<D> / 32;          // sampled key blocks per tile
@@ -519,7 +538,8 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   constexpr int kInstPerWave = kTileBytes / 1024 / kPWaves;
   constexpr int kBufs = kPBufs<D>;                    // tile t read, the younger ones in flight
   constexpr int KQ = kQPW<D>;                         // sampled q-blocks per wave
-  constexpr int kSt = KQ * (kKT / 2);                 // R stores per wave and tile
+  // R stores per wave and LDS tile: one per pair of 32-key tiles; at 16 one per 32-key tile
+  constexpr int kSt = kKeep == 16 ? kKT : KQ * (kKT / 2);
   // LDS: m [4][32] f32 | K tiles x4 (after the main loop: per-wave row scratch). The per-row
   // block maxima R go to a global scratch in [key block][32 rows] order (as the Triton kernel keeps
   // R in HBM): a tile's two columns are one contiguous 128-byte store, and the LDS stays small
@@ -559,14 +579,15 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   const int l32 = lane & 31;
   // XCD-aware order: give each XCD a contiguous range of (head, q-group) work, so a head's sampled
   // keys are re-read from that XCD's own L2. Placement only affects speed.
-  const int nqg = (nb + kPWaves * KQ - 1) / (kPWaves * KQ);
+  const int ng = kKeep == 64 ? 2 * nb : kKeep == 16 ? (nb + 1) >> 1 : nb;   // 32-row groups of the q stream
+  const int nqg = (ng + kPWaves * KQ - 1) / (kPWaves * KQ);
   const int lin = xcd_linear(wg, nqg * p.B * p.H);
   const int bh = lin / nqg;
-  int qbs[KQ];   // this wave's sampled q-blocks
+  int qbs[KQ];   // this wave's 32-row groups of the sampled q stream (at kKeep 32: its q-blocks)
 #pragma unroll
   for (int e = 0; e < KQ; ++e) qbs[e] = (lin % nqg) * kPWaves * KQ + wave * KQ + e;
 #if !VB_PRED_GATHER
-  const int64_t slice = (int64_t)nb * 32 * kRowB;   // bytes of one (b,h) sampled stream
+  const int64_t slice = (int64_t)nb * kKeep * kRowB;   // bytes of one (b,h) sampled stream
 #endif
 
   // Q fragment of this lane's sampled row (B operand of S^T = K_s . Q_s^T), gathered straight from
@@ -575,7 +596,10 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
 #pragma unroll
   for (int e = 0; e < KQ; ++e) {
     const int b = bh / p.H, h = bh % p.H;
-    const int qrow = sampled_row(qbs[e] < nb ? qbs[e] : 0, p.q_off[(int64_t)bh * 32 + l32], p.block, p.L, p.rows);
+    // the lane's row of the sampled q stream is qbs[e]*32 + l32: q-block and token of that row
+    const int qb_l = kKeep == 64 ? qbs[e] >> 1 : kKeep == 16 ? 2 * qbs[e] + (l32 >> 4) : qbs[e];
+    const int qt_l = kKeep == 64 ? (qbs[e] & 1) * 32 + l32 : kKeep == 16 ? (l32 & 15) : l32;
+    const int qrow = sampled_row(qb_l < nb ? qb_l : 0, p.q_off[(int64_t)bh * kKeep + qt_l], p.block, p.L, p.rows);
     const uint8_t* qp = reinterpret_cast<const uint8_t*>(p.q) + 2 * (b * p.qs[0] + h * p.qs[1] + (int64_t)qrow * p.qs[2]);
 #pragma unroll
     for (int s = 0; s < KS; ++s)
@@ -596,7 +620,7 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   constexpr int kChunks = kRowB / 16;
   const uint8_t* kslice = reinterpret_cast<const uint8_t*>(p.k) + 2 * ((bh / p.H) * p.ks[0] + (bh % p.H) * p.ks[1]);
   const srd_t ksrd = make_srd(kslice, (int)((int64_t)(p.L - 1) * p.ks[2] * 2 + kRowB));
-  const srd_t isrd = make_srd(reinterpret_cast<const int32_t*>(p.k_s) + (int64_t)bh * nb * 32, nb * 32 * 4);
+  const srd_t isrd = make_srd(reinterpret_cast<const int32_t*>(p.k_s) + (int64_t)bh * nb * kKeep, nb * kKeep * 4);
   uint8_t* ibuf = ktile + kBufs * kTileBytes + wave * 256;   // [4 tiles][4 waves][64 dwords]
   int cv[kInstPerWave];   // the lane's swizzled chunk within its row, per DMA instruction
 #pragma unroll
@@ -624,7 +648,9 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   for (int e = 0; e < KQ; ++e) m[e] = -INFINITY;
   __syncthreads();   // all plain global loads retired before the DMA pipeline
 
-  const int ntiles = (VB_DIAG && (p.dbg & 2)) ? 0 : (nb + kKT - 1) / kKT;
+  // LDS tiles of the nb*kKeep-row sampled K stream (kKT 32-key tiles each)
+  const int nkt = kKeep == 64 ? 2 * nb : kKeep == 16 ? (nb + 1) >> 1 : nb;
+  const int ntiles = (VB_DIAG && (p.dbg & 2)) ? 0 : (nkt + kKT - 1) / kKT;
   // K tile t by LDS-DMA (global_load_lds_dwordx4): the LDS image is written linearly (1 KiB per
   // wave-instruction), so the 16-byte-chunk XOR swizzle of the image is applied to each lane's
   // SOURCE address: LDS slot `sl` of row r holds chunk sl ^ sw(r).
@@ -664,9 +690,23 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   srd_t rsrd[KQ];
 #pragma unroll
   for (int e = 0; e < KQ; ++e) {
-    Rqs[e] = p.rbuf + ((int64_t)bh * nb + (qbs[e] < nb ? qbs[e] : 0)) * nb * 32;
-    rsrd[e] = make_srd(Rqs[e], qbs[e] < nb ? nb * 64 : 0);
+    if constexpr (kKeep == 32) {
+      Rqs[e] = p.rbuf + ((int64_t)bh * nb + (qbs[e] < nb ? qbs[e] : 0)) * nb * 32;
+      rsrd[e] = make_srd(Rqs[e], qbs[e] < nb ? nb * 64 : 0);
+    } else {
+      // the slice of the group's first q-block; at 16 the descriptor spans the group's two q-blocks
+      // (one when nb is odd and the group is the last: the lanes of the missing one fall outside)
+      const int qb0 = kKeep == 64 ? qbs[e] >> 1 : 2 * qbs[e];
+      const int nqb = kKeep == 64 ? 1 : min(2, nb - qb0);
+      Rqs[e] = p.rbuf + ((int64_t)bh * nb + (qbs[e] < ng ? qb0 : 0)) * nb * kKeep;
+      rsrd[e] = make_srd(Rqs[e], qbs[e] < ng ? nqb * nb * kKeep * 2 : 0);
+    }
   }
+  // the lane's byte offset within a key block's column of R (plus, at 16, its q-block's slice); lanes
+  // that must not store get kNoStore, outside any descriptor whatever the tile's offset adds
+  [[maybe_unused]] constexpr int kNoStore = 0x40000000;
+  [[maybe_unused]] const int rv = kKeep == 64 ? ((qbs[0] & 1) * 32 + l32) * 2
+               : kKeep == 16 ? ((l32 >> 4) * nb * 16 + half * 16 + (l32 & 15)) * 2 : lane * 2;
 #if VB_PRED_GATHER
   // Issue order: I0 I1 I2 K0 K1, then per body t: I(t+3) K(t+2) [compute] S(t) — every DMA is
   // issued, past the last tile too (offsets past the table read 0: row 0 into a slot no tile reads
@@ -781,6 +821,39 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
     // 2pr's full row max and lanes 32-63 block 2pr+1's (the halves of each block's C tile meet)
     const int j0 = kKT * t;
     constexpr int kPairs = kKT / 2;
+    if constexpr (kKeep == 64) {
+      // a key block is the pair of tiles 2pr, 2pr+1: the maximum over both tiles' registers, then
+      // over the two lane halves, so every lane holds its query row's maximum over the block's 64 keys
+#pragma unroll
+      for (int pr = 0; pr < kPairs; ++pr) {
+        const float x = fmaxf(halfmax(sc[0][2 * pr]), halfmax(sc[0][2 * pr + 1]));
+        float mx = max_xor32(x) * p.c;
+        const int jb = kPairs * t + pr;   // wave-uniform
+        if (jb >= nb) mx = -INFINITY;     // partial last tile (D=64, odd nb)
+        m[0] = fmaxf(m[0], mx);
+        // R[jb][64 rows]: the wave's 32 rows (both halves store the same value to the same bytes).
+        // One store per pair, issued unconditionally as below.
+        store16(rsrd[0], (uint16_t)storage_bits<T>(mx), jb < nb ? rv : kNoStore, jb * 128);
+      }
+    } else if constexpr (kKeep == 16) {
+      // a 32-key tile is two key blocks: accumulator registers 0-7 are key rows 0-15 of the tile (of
+      // both halves), 8-15 rows 16-31. After the swap lanes 0-31 hold the first block's row maximum
+      // and lanes 32-63 the second's, for query l32 (q-block 2g + (l32 >> 4), row l32 & 15).
+#pragma unroll
+      for (int kt = 0; kt < kKT; ++kt) {
+        const f32x16& a = sc[0][kt];
+        const float lo = fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(a[4], a[5]), fmaxf(a[6], a[7])));
+        const float hi = fmaxf(fmaxf(fmaxf(a[8], a[9]), fmaxf(a[10], a[11])), fmaxf(fmaxf(a[12], a[13]), fmaxf(a[14], a[15])));
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+        float mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * p.c;
+        const int jb = 2 * (j0 + kt) + half;
+        if (jb >= nb) mx = -INFINITY;   // half a tile of keys past an odd nb, and whole tiles past it
+        m[0] = fmaxf(m[0], mx);         // this half's key blocks; halves meet below
+        // R[q-block][jb][16 rows]: kKT stores per body, issued unconditionally; a lane whose key block
+        // is past nb stores nowhere, one whose q-block is past nb falls outside the descriptor
+        store16(rsrd[0], (uint16_t)storage_bits<T>(mx), jb < nb ? rv : kNoStore, (j0 + kt) * 64);
+      }
+    } else {
 #pragma unroll
     for (int q = 0; q < KQ; ++q) {
     float mxp[kKT / 2];
@@ -804,6 +877,7 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
     // hardware drops those lanes.
 #pragma unroll
     for (int pr = 0; pr < kPairs; ++pr) store16(rsrd[q], (uint16_t)storage_bits<T>(mxp[pr]), lane * 2, (j0 + 2 * pr) * 64);
+    }
     }
 
 #if VB_PRED_STAMPS
@@ -843,43 +917,56 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
   auto epilogue = [&](const int qb, const uint16_t* Rq, const float* mw) __attribute__((always_inline)) {
     // this wave's R columns were stored by its own lanes: wait for them and drop any stale L1 line
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    float mreg[32];
+    // the q-block's kKeep rows in sweeps of kER: at 64 the first sweep leaves max_r (R - m_r) over
+    // rows 0-31 in val[], the second joins rows 32-63 (the other wave's, behind the barrier above)
+    constexpr int kER = kKeep == 16 ? 16 : 32;
+    float part = 0.f;
 #pragma unroll
-    for (int r = 0; r < 32; r += 4) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(mw + r);
+    for (int sw = 0; sw < kKeep / kER; ++sw) {
+    float mreg[kER];
+#pragma unroll
+    for (int r = 0; r < kER; r += 4) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(mw + kER * sw + r);
 #pragma unroll
       for (int e = 0; e < 4; ++e) mreg[r + e] = x[e];
     }
-    float part = 0.f;
     // VB_PRED_RCOLS columns per lane per pass (4 loads each in flight): the block's 32 row maxima
     // are 64 contiguous bytes
     constexpr int kRC = VB_PRED_RCOLS;
     for (int j0 = 0; j0 < nb; j0 += 64 * kRC) {
-      u32x4 w[kRC][4];
+      u32x4 w[kRC][kER / 8];
 #pragma unroll
       for (int h = 0; h < kRC; ++h) {
         const int jj = min(j0 + 64 * h + lane, nb - 1);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) w[h][c] = reinterpret_cast<const u32x4*>(Rq + jj * 32)[c];
+        for (int c = 0; c < kER / 8; ++c) w[h][c] = reinterpret_cast<const u32x4*>(Rq + jj * kKeep + kER * sw)[c];
       }
 #pragma unroll
       for (int h = 0; h < kRC; ++h) {
         const int j = j0 + 64 * h + lane;
         float cm = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < kER / 8; ++c)
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = 8 * c + 2 * e;
             cm = max3f(cm, T::bits_to_f32((uint16_t)(w[h][c][e] & 0xFFFF)) - mreg[r],
                        T::bits_to_f32((uint16_t)(w[h][c][e] >> 16)) - mreg[r + 1]);
           }
+        if constexpr (kKeep == 64) {
+          if (sw == 0) {
+            if (j < nb) val[j] = cm;
+            continue;
+          }
+          if (j < nb) cm = fmaxf(cm, val[j]);
+        }
         cm = round_to<T>(exp2_fast(cm));
         if (j < nb) {
           val[j] = cm;
           part += cm;
         }
       }
+    }
     }
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
     const float tot = round_to<T>(part);
@@ -913,9 +1000,19 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
     if (p.count && lane == 0) atomicAdd(p.count, (unsigned long long)kept);
     if (p.rows_kept && lane == 0) p.rows_kept[(int64_t)bh * nb + qb] = kept;
   };
+  if constexpr (kKeep == 64) {
+    // the even wave of a pair holds the q-block's rows 0-31, its neighbour rows 32-63 (ng is even, so
+    // both are live); their row maxima are 64 consecutive floats of mrow_s. The neighbour's R stores
+    // were retired (vmcnt(0)) before the barrier above.
+    if (qbs[0] < ng && !(wave & 1)) epilogue(qbs[0] >> 1, Rqs[0], mrow_s + wave * 32);
+  } else if constexpr (kKeep == 16) {
+    for (int s = 0; s < 2; ++s)   // the group's two q-blocks: rows 16s.. of the tile
+      if (2 * qbs[0] + s < nb) epilogue(2 * qbs[0] + s, Rqs[0] + s * nb * 16, mrow_s + wave * 32 + 16 * s);
+  } else {
 #pragma unroll
   for (int e = 0; e < KQ; ++e)
     if (qbs[e] < nb) epilogue(qbs[e], Rqs[e], mrow_s + (wave * KQ + e) * 32);
+  }
   VB_TRACE_END();
 }
 
@@ -968,14 +1065,15 @@ static size_t predict_smem_bytes(int nb, int D, bool long_rows) {
   return mrow + (tiles + ring > scratch ? tiles + ring : scratch);
 }
 
-// workspace: sampled k rows (gather mode: their int32 byte offsets) | R
-static uint64_t predict_rows_bytes(int B, int H, int L, int D) {
+// workspace: sampled k rows (gather mode: their int32 byte offsets) | R; both scale with the
+// sampling density `keep` (rows per block)
+static uint64_t predict_rows_bytes(int B, int H, int L, int D, int keep) {
   const int nb = (L + 127) / 128;
-  return (uint64_t)B * H * nb * 32 * (VB_PRED_GATHER ? 4 : D * 2);
+  return (uint64_t)B * H * nb * keep * (VB_PRED_GATHER ? 4 : D * 2);
 }
-static uint64_t predict_ws_bytes(int B, int H, int L, int D) {
+static uint64_t predict_ws_bytes(int B, int H, int L, int D, int keep) {
   const uint64_t nb = (L + 127) / 128;
-  return predict_rows_bytes(B, H, L, D) + (uint64_t)B * H * nb * nb * 32 * 2;
+  return predict_rows_bytes(B, H, L, D, keep) + (uint64_t)B * H * nb * nb * keep * 2;
 }
 
 // B*H*block bound of the in-kernel Philox draws (see vb_mask_predict), per device, cached
@@ -993,19 +1091,20 @@ static int64_t philox_x_only_numel() {
   return n;
 }
 
-template <int D, class T, bool kLong>
+template <int D, class T, bool kLong, int kKeep = 32>
 static int launch_predict(const PredParams& p, hipStream_t stream, hipEvent_t staged) {
   const size_t smem = predict_smem_bytes(p.nb, D, kLong);
-  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY, kLong>;
+  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY, kLong, kKeep>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)smem) != hipSuccess)
     return fail(VB_ERR_LAUNCH, "mask_predict: cannot reserve LDS");
-  hipLaunchKernelGGL(sample_rows_kernel<T>, dim3((unsigned)((p.nb * 32 + 255) / 256), (unsigned)(p.B * p.H)), dim3(256),
-                     0, stream, p);
+  hipLaunchKernelGGL((sample_rows_kernel<T, kKeep>), dim3((unsigned)((p.nb * kKeep + 255) / 256), (unsigned)(p.B * p.H)),
+                     dim3(256), 0, stream, p);
   if (int rc = check_launch("sample_rows_kernel")) return rc;
   if (staged && hipEventRecord(staged, stream) != hipSuccess) return fail(VB_ERR_LAUNCH, "vb_mask_predict: hipEventRecord failed");
-  constexpr int qpw = kPWaves * kQPW<D>;   // sampled q-blocks per workgroup
-  const dim3 grid(((p.nb + qpw - 1) / qpw) * p.B * p.H + p.n_pool);
+  constexpr int qpw = kPWaves * kQPW<D>;   // 32-row groups of the sampled q stream per workgroup
+  const int ng = (p.nb * kKeep + 31) / 32;
+  const dim3 grid(((ng + qpw - 1) / qpw) * p.B * p.H + p.n_pool);
   hipLaunchKernelGGL(kern, grid, dim3(kPThreads), smem, stream, p);
   if (int rc = check_launch("mask_predict_kernel")) return rc;
   if (VB_PRED_SPLIT_ENERGY && p.mask) {
@@ -1032,8 +1131,8 @@ extern "C" int vb_debug_pred_stamps(unsigned long long* out) {
 #endif
 
 extern "C" uint64_t vb_mask_predict_workspace_size(const vb_predict_args* a) {
-  if (!a || a->B <= 0 || a->H <= 0 || a->L <= 0 || a->D <= 0) return 0;
-  return vb::predict_ws_bytes(a->B, a->H, a->L, a->D);
+  if (!a || a->B <= 0 || a->H <= 0 || a->L <= 0 || a->D <= 0 || a->num_keep <= 0) return 0;
+  return vb::predict_ws_bytes(a->B, a->H, a->L, a->D, a->num_keep);
 }
 
 // vb_mask_predict and vb_mask_predict_long: one validation and parameter set-up, `fn` names the entry
@@ -1045,8 +1144,9 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
   if (!a || !a->q || !a->k || !a->q_off || !a->k_off || !a->po)
     return fail(VB_ERR_INVALID, fn + "null argument");
   if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, fn + "bad sizes");
-  if (a->block != 128 || a->num_keep != 32)
-    return fail(VB_ERR_UNSUPPORTED, fn + "block must be 128 and num_keep 32 (the reference's values)");
+  if (a->block != 128 || (a->num_keep != 16 && a->num_keep != 32 && a->num_keep != 64))
+    return fail(VB_ERR_UNSUPPORTED, fn + "block must be 128 and num_keep 16, 32 or 64 (got block " +
+                                        std::to_string(a->block) + ", num_keep " + std::to_string(a->num_keep) + ")");
   const int nb = (a->L + a->block - 1) / a->block;
   if (nb > (kLong ? kMaxNbLong : kMaxNb)) return fail(VB_ERR_UNSUPPORTED, fn + "sequence too long");
   // The short entry's L < 65536 guard came with the packed sort keys. Audit of every 16-bit quantity
@@ -1057,10 +1157,10 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
   if (!kLong && a->L > 65535) return fail(VB_ERR_UNSUPPORTED, fn + "L must be < 65536");
   if (a->min_keep < 1 || a->max_keep < 1) return fail(VB_ERR_INVALID, fn + "keep counts must be >= 1");
   if (a->D != 64 && a->D != 128) return fail(VB_ERR_UNSUPPORTED, fn + "head_dim must be 64 or 128");
-  const uint64_t ws = predict_ws_bytes(a->B, a->H, a->L, a->D);
+  const uint64_t ws = predict_ws_bytes(a->B, a->H, a->L, a->D, a->num_keep);
   if (!a->workspace || a->workspace_bytes < ws || (reinterpret_cast<uintptr_t>(a->workspace) & 15))
     return fail(VB_ERR_INVALID, fn + "workspace missing or smaller than vb_mask_predict_workspace_size()");
-  const uint64_t rows_b = predict_rows_bytes(a->B, a->H, a->L, a->D);
+  const uint64_t rows_b = predict_rows_bytes(a->B, a->H, a->L, a->D, a->num_keep);
   if (rows_b / a->B / a->H >= (uint64_t(1) << 31)) return fail(VB_ERR_UNSUPPORTED, fn + "sampled stream too large");
   if ((int64_t)(a->L - 1) * a->k_stride[2] * 2 + 2 * a->D >= (int64_t(1) << 31))
     return fail(VB_ERR_UNSUPPORTED, fn + "a k (b,h) slice spans >= 2 GiB");
@@ -1161,6 +1261,22 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
 #endif
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipEvent_t ev = reinterpret_cast<hipEvent_t>(a->staged_event);
+  if (a->dtype != VB_DTYPE_BF16 && a->dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, fn + "unknown dtype");
+  if (a->num_keep != 32) {
+#if VB_PRED_GATHER && VB_PRED_QPW64 == 1
+    // densities 16 and 64 exist in the long instantiation only (it writes the short one's bits for
+    // nb <= kMaxNb); the entry's own row limit was checked above
+    const bool bf = a->dtype == VB_DTYPE_BF16;
+    if (a->num_keep == 16) {
+      if (a->D == 64) return bf ? launch_predict<64, BF16, true, 16>(p, s, ev) : launch_predict<64, F16, true, 16>(p, s, ev);
+      return bf ? launch_predict<128, BF16, true, 16>(p, s, ev) : launch_predict<128, F16, true, 16>(p, s, ev);
+    }
+    if (a->D == 64) return bf ? launch_predict<64, BF16, true, 64>(p, s, ev) : launch_predict<64, F16, true, 64>(p, s, ev);
+    return bf ? launch_predict<128, BF16, true, 64>(p, s, ev) : launch_predict<128, F16, true, 64>(p, s, ev);
+#else   // diagnostic builds with the sampled-row copy or two q-blocks per wave
+    return fail(VB_ERR_UNSUPPORTED, fn + "this build variant has num_keep 32 only");
+#endif
+  }
   if (a->dtype == VB_DTYPE_BF16) {
     if (a->D == 64) return launch_predict<64, BF16, kLong>(p, s, ev);
     if (a->D == 128) return launch_predict<128, BF16, kLong>(p, s, ev);

@@ -122,6 +122,9 @@ class AdaptiveBlockSparseAttn(nn.Module):
 
     variant: "cog" (CogVideoX-5B: text tail, forced last 2 block rows/cols) or "wan"
     (Wan2.1-1.3B). Keyword arguments override the reference's module globals.
+    num_keep: tokens the mask predictor samples per 128-token block, 16, 32 (default, the
+    reference's) or 64: a quarter / four times the predictor's score work. Given q_off/k_off must
+    be [B,H,num_keep].
     combine: "fused" (one softmax, inference default) or "reference" (two attention calls + the
     reference's bf16 LSE combine, bit-for-bit structure of :366-393; always used under autograd).
     mask_head_mode: how the reference's head_mask_type = ones(H) (:313) reads the predicted
@@ -152,8 +155,9 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self.energy_threshold = float(cfg.get("energy_threshold", 0.95))
         self.block = int(cfg.get("block", 128))
         self.num_keep = int(cfg.get("num_keep", 32))
-        if self.block != 128 or self.num_keep != 32:
-            raise ValueError("block=128 and num_keep=32 are the reference's (only) values")
+        if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
+            raise ValueError(f"block must be 128 (the reference's only value) and num_keep one of "
+                             f"{ops.NUM_KEEP_VALUES} (the reference's default is 32)")
         self.log_every = int(cfg["log_every"])
         self.mask_head_mode = cfg.get("mask_head_mode", "per_head")
         ops.mask_head_mode_code(self.mask_head_mode)   # validates
@@ -256,16 +260,17 @@ class AdaptiveBlockSparseAttn(nn.Module):
                 rand = (torch.rand(B, H, 1, self.block, device=q.device),
                         torch.rand(B, H, 1, self.block, device=q.device))
         elif q_off is None:
-            q_off = draw_sample_offsets(B, H, q.device)
+            q_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
         elif k_off is None:
-            k_off = draw_sample_offsets(B, H, q.device)
+            k_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
         nb = (L + self.block - 1) // self.block
         lo, hi = retain_counts(nb, self.min_retain_ratio, self.max_retain_ratio, self.variant)
         po, mask = ops.mask_predict(q, k, q_off, k_off, rows=self._rows(q.device),
                                     energy_threshold=self.energy_threshold, min_keep=lo,
                                     max_keep=hi, force_tail=self.force_tail, mask_count=count,
                                     staged_event=staged_event, rand=rand, philox=philox,
-                                    pool=pool, rows_kept=rows_kept, long_rows=nb > ops.MAX_BLOCKS)
+                                    pool=pool, rows_kept=rows_kept, long_rows=nb > ops.MAX_BLOCKS,
+                                    num_keep=self.num_keep)
         return po, mask
 
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *,

@@ -46,10 +46,12 @@ def density(mask_ratios=None) -> float:
     return sum((e - s) / v for v, (s, e) in r.items() if v != 0)
 
 
-def predict_level_mask(q, k, *, rows=None, mask_ratios=None, q_off=None, k_off=None, pyr=None):
+def predict_level_mask(q, k, *, rows=None, mask_ratios=None, q_off=None, k_off=None, pyr=None,
+                       num_keep=32):
     """efficient_attn_with_pooling + transfer_attn_to_mask on the (reordered through ``rows``)
     q, k: returns (po [B,H,nb,nb] q.dtype, level mask uint8 [B,H,nb,nb]). ``pyr=(v, outs)``: the
-    KV pyramid pass in the score kernel's launch (ops.mask_predict)."""
+    KV pyramid pass in the score kernel's launch (ops.mask_predict). ``num_keep``: sampled tokens
+    per block (16, 32 or 64; given offsets must be that wide)."""
     B, H, L, D = q.shape
     rand = philox = None
     if q_off is None and k_off is None:
@@ -59,20 +61,21 @@ def predict_level_mask(q, k, *, rows=None, mask_ratios=None, q_off=None, k_off=N
         if philox is None:
             rand = (torch.rand(B, H, 1, BLOCK, device=q.device), torch.rand(B, H, 1, BLOCK, device=q.device))
     elif q_off is None or k_off is None:
-        q_off, k_off = draw_sample_offsets_qk(B, H, q.device, BLOCK, 32)
+        q_off, k_off = draw_sample_offsets_qk(B, H, q.device, BLOCK, num_keep)
     # the rank-band level mask comes out of the score kernel's epilogue (vb_predict_args.mask_level;
     # ops.level_mask is the stand-alone form of the same rule)
     long_rows = (L + BLOCK - 1) // BLOCK > ops.MAX_BLOCKS   # past vb_mask_predict's rows: the long entry
     if not FUSED_LEVEL_MASK:
         po, _ = ops.mask_predict(q, k, q_off, k_off, rows=rows, want_mask=False, rand=rand, philox=philox,
-                                 pyr=pyr, long_rows=long_rows)
+                                 pyr=pyr, long_rows=long_rows, num_keep=num_keep)
         return po, ops.level_mask(po, mask_ratios)
     return ops.mask_predict(q, k, q_off, k_off, rows=rows, rand=rand, philox=philox, pyr=pyr,
-                            level=MASK_RATIOS if mask_ratios is None else mask_ratios, long_rows=long_rows)
+                            level=MASK_RATIOS if mask_ratios is None else mask_ratios, long_rows=long_rows,
+                            num_keep=num_keep)
 
 
 def adaptive_block_sparse_attn(q, k, v, *, rows=None, mask_ratios=None, ref_tail=True,
-                               q_off=None, k_off=None, return_mask=False):
+                               q_off=None, k_off=None, return_mask=False, num_keep=32):
     """adaptive_block_sparse_attn (Triton/cogvideo_newattn.py:210-234), inference.
 
     ``rows`` (optional int32 [L]) applies the Gilbert reorder inside the kernels: reordered row g
@@ -80,7 +83,7 @@ def adaptive_block_sparse_attn(q, k, v, *, rows=None, mask_ratios=None, ref_tail
     rearrange -> this function -> reversed_rearrange without the copies."""
     with torch.no_grad():
         po, mask = predict_level_mask(q, k, rows=rows, mask_ratios=mask_ratios, q_off=q_off,
-                                      k_off=k_off)
+                                      k_off=k_off, num_keep=num_keep)
         kpyr, vpyr = ops.kv_pyramid(k, v, rows)
         out = ops.ml_attention_fwd(q, kpyr, vpyr, mask, q_rows=rows, ref_tail=ref_tail)
     sp = 1.0 - density(mask_ratios)
@@ -133,8 +136,9 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
     include/vblade.h, vb_ml_attn_fwd)."""
 
     def __init__(self, *, mask_ratios=None, ref_tail: bool = True, log_every: int = 600,
-                 overlap: bool = True, persistent: bool = False, **overrides):
-        """overlap: run the KV pyramid pass inside the predictor's launch (True) or as its own
+                 overlap: bool = True, persistent: bool = False, num_keep: int = 32, **overrides):
+        """num_keep: tokens the mask predictor samples per block (16, 32 or 64; default 32).
+        overlap: run the KV pyramid pass inside the predictor's launch (True) or as its own
         launch after it. persistent: the attention launch is resident-sized and pulls q-blocks
         from per-XCD work queues (scheduling only; see attention.PERSISTENT_DEFAULT)."""
         super().__init__()
@@ -158,6 +162,9 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
         self._attn_launches = 0
         self.overlap = bool(overlap)
         self.persistent = bool(persistent)
+        self.num_keep = int(num_keep)
+        if self.num_keep not in ops.NUM_KEEP_VALUES:
+            raise ValueError(f"num_keep must be one of {ops.NUM_KEEP_VALUES}")
 
     def _rows(self, device):
         if not self.use_rearrange:
@@ -179,7 +186,8 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
             with torch.no_grad():
                 if level_mask is None:
                     _, mask = predict_level_mask(q.detach(), k.detach(), rows=rows,
-                                                 mask_ratios=self.mask_ratios, q_off=q_off, k_off=k_off)
+                                                 mask_ratios=self.mask_ratios, q_off=q_off, k_off=k_off,
+                                                 num_keep=self.num_keep)
                 else:
                     mask = level_mask.to(torch.uint8).contiguous()
             out = _SparseAttention.apply(q, k, v, mask, q.shape[-1] ** -0.5, self.ref_tail, rows)
@@ -194,7 +202,8 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
             if level_mask is None:
                 _, mask = predict_level_mask(q, k, rows=rows, mask_ratios=self.mask_ratios,
                                              q_off=q_off, k_off=k_off,
-                                             pyr=(v, outs) if self.overlap else None)
+                                             pyr=(v, outs) if self.overlap else None,
+                                             num_keep=self.num_keep)
             else:
                 mask = level_mask.to(torch.uint8).contiguous()
             if level_mask is None and self.overlap:

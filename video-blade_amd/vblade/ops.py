@@ -17,6 +17,7 @@ from . import _lib
 from ._lib import AttnArgs, BwdArgs, MlAttnArgs, MlBwdArgs, PredictArgs, check
 
 BLOCK = 128
+NUM_KEEP_VALUES = (16, 32, 64)   # sampled tokens per block the predictor is built for (default 32)
 MAX_BLOCKS = 320         # vb_mask_predict's rows (L <= 40960)
 MAX_BLOCKS_LONG = 1024   # vb_mask_predict_long's, the attention kernels' own limit (L <= 131072)
 
@@ -359,8 +360,8 @@ def block_sparse_attn_bwd(dout, q_unpad, k_unpad, v_unpad, out_unpad, softmax_ls
 def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.95, min_keep=1,
                  max_keep=1, force_tail=0, scale=None, mask_count=None, want_mask=True,
                  staged_event=None, rand=None, philox=None, pool=None, pyr=None, level=None,
-                 rows_kept=None, long_rows=False):
-    """vb_mask_predict. q,k [B,H,L,D]; q_off/k_off int32 [B,H,32]. Returns (po, mask) with
+                 rows_kept=None, long_rows=False, num_keep=None):
+    """vb_mask_predict. q,k [B,H,L,D]; q_off/k_off int32 [B,H,num_keep]. Returns (po, mask) with
     po [B,H,nb,nb] in q.dtype and mask uint8 [B,H,nb,nb] (None with want_mask=False: the scores
     only, no energy rule). ``staged_event`` (a torch.cuda.Event) is recorded once the sampled
     rows are staged, before the score kernel: work waiting on it overlaps the score kernel.
@@ -378,13 +379,19 @@ def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.
     on the scores, computed by the score kernel's epilogue) instead of the energy mask.
     ``rows_kept``: int32 [B,H,nb] receiving the energy rule's kept-block count per mask row.
     ``long_rows``: call vb_mask_predict_long (up to MAX_BLOCKS_LONG = 1024 blocks, L <= 131072; the
-    same outputs) instead of vb_mask_predict (up to MAX_BLOCKS = 320 blocks, L <= 40960)."""
+    same outputs) instead of vb_mask_predict (up to MAX_BLOCKS = 320 blocks, L <= 40960).
+    ``num_keep``: sampled tokens per 128-token block, one of NUM_KEEP_VALUES = (16, 32, 64): a quarter
+    / four times the score work of the default 32 (the reference's value). With ``rand=`` or
+    ``philox=`` it is the width of the offsets drawn (default 32; the draws stay [B,H,1,block]);
+    with given offsets the width is read from q_off.shape[-1], which k_off and an explicit
+    ``num_keep`` must match (ValueError otherwise). The library refuses other widths
+    (VB_ERR_UNSUPPORTED)."""
     try:
         return _mask_predict(q, k, q_off, k_off, rows=rows, energy_threshold=energy_threshold,
                              min_keep=min_keep, max_keep=max_keep, force_tail=force_tail, scale=scale,
                              mask_count=mask_count, want_mask=want_mask, staged_event=staged_event,
                              rand=rand, philox=philox, pool=pool, pyr=pyr, level=level,
-                             rows_kept=rows_kept, long_rows=long_rows)
+                             rows_kept=rows_kept, long_rows=long_rows, num_keep=num_keep)
     except Exception as e:
         # the claimed draws go back to the generator only when nothing was launched: a Python-side
         # error (validation, or a host-side VBladeError such as the library failing to load, code
@@ -398,9 +405,29 @@ def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.
         raise
 
 
+def _offset_width(q_off, k_off, num_keep, drawn: bool) -> int:
+    """The sampling density of a mask_predict call: ``num_keep`` (default 32) when the offsets are
+    drawn in the launch, else the given offsets' common width. Which widths exist is the library's
+    decision (NUM_KEEP_VALUES; VB_ERR_UNSUPPORTED otherwise)."""
+    if drawn:
+        keep = 32 if num_keep is None else int(num_keep)
+        if keep <= 0:
+            raise ValueError(f"mask_predict: num_keep must be one of {NUM_KEEP_VALUES}, got {num_keep}")
+        return keep
+    if q_off is None or k_off is None:
+        raise ValueError("mask_predict: give q_off and k_off, or rand= or philox=")
+    if q_off.shape[-1] != k_off.shape[-1]:
+        raise ValueError(f"mask_predict: q_off and k_off must have the same width, got "
+                         f"{q_off.shape[-1]} and {k_off.shape[-1]}")
+    if num_keep is not None and int(num_keep) != q_off.shape[-1]:
+        raise ValueError(f"mask_predict: the offsets are {q_off.shape[-1]} wide, num_keep={num_keep}")
+    return int(q_off.shape[-1])
+
+
 def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_keep, force_tail,
                   scale, mask_count, want_mask, staged_event, rand, philox, pool, pyr, level, rows_kept,
-                  long_rows=False):
+                  long_rows=False, num_keep=None):
+    keep = _offset_width(q_off, k_off, num_keep, drawn=rand is not None or philox is not None)
     if k.shape != q.shape:
         raise ValueError(f"mask_predict: k and v must have q's shape {tuple(q.shape)}, "
                          f"got k {tuple(k.shape)}")
@@ -418,8 +445,8 @@ def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_k
     if rand is not None or philox is not None:
         if rand is not None:
             rand_q, rand_k = (r.float().contiguous() for r in rand)
-        q_off = torch.empty(B, H, 32, device=dev, dtype=torch.int32)
-        k_off = torch.empty(B, H, 32, device=dev, dtype=torch.int32)
+        q_off = torch.empty(B, H, keep, device=dev, dtype=torch.int32)
+        k_off = torch.empty(B, H, keep, device=dev, dtype=torch.int32)
     q_off = q_off.to(torch.int32).contiguous()
     k_off = k_off.to(torch.int32).contiguous()
     a = PredictArgs()
