@@ -249,6 +249,83 @@ def multilevel_attention_bwd(q, k, v, mask, out, l, m, dout, sm_scale=None, stor
     return dq, dk[:, :, :L], dv[:, :, :L]
 
 
+def multilevel_attention_bwd_lse(q, k, v, mask, out, lse, dout, sm_scale=None, ref_tail=True,
+                                 store_dtype=torch.bfloat16, emulate_rounding=False,
+                                 fold_weights=(1.0, 0.5, 0.25, 0.125)):
+    """Op-level statement of vb_ml_attn_bwd (include/vblade.h) in fp64, every tensor in REORDERED row
+    order: the gradient w.r.t. q, k, v [B,H,L,D] of the multi-level attention under ``mask``
+    [B,H,nb,nb], in FlashAttention-2 form from the forward's own ``out`` [B,H,L,D] and ``lse``
+    [B,H,L] (as vb_ml_attn_fwd wrote them): P = exp(S*scale + ln p - lse), Delta = rowsum(dO*out),
+    dS = P*(dO.V^T - Delta). Rows with lse = +-inf contribute nothing.
+
+    One key axis of 15*Lpad/8 rows holds the four pyramid levels (level-1 rows >= L zero, as the
+    kernels' pyramid stores them), each key with the bias ln p of its level; a key is live for
+    q-block i iff mask[i, its block] == its level (values other than 1, 2, 4, 8 keep nothing), and
+    with ``ref_tail=False`` level-1 keys >= L are dead. The pyramid-row gradients fold back as
+    dk[r] = dK1[r] + dK2[r/2]/2 + dK4[r/4]/4 + dK8[r/8]/8 for r < L (the gradient reaching the
+    replicate-padded rows is dropped, as the reference does).
+
+    ``emulate_rounding``: the same, rounded to ``store_dtype`` exactly where the multi-level kernels
+    round (csrc/vb_attn_bwd.hip bwd_dkdv_kernel / bwd_dq_kernel and their pipeline forms in
+    csrc/vb_attn_bwd_kv.hip): P and dS as MFMA operands (pack8 / pack2 before the dV, dK and dQ
+    products; dS is formed from the unrounded P), and dq, dk, dv once (pack2 in the epilogues), dk/dv
+    after the fold. The pooled levels' partials stay fp32 (dkpyr/dvpyr) and the fold is an fp32 fma
+    chain, so the multi-level instantiations add no rounding step to the two-branch ones.
+    ``fold_weights``: the fold's per-level weights; anything but the default is a deliberately
+    wrong reference for testing the error metric. Returns fp32 (dq, dk, dv)."""
+    B, H, L, D = q.shape
+    scale = sm_scale if sm_scale is not None else D ** -0.5
+    nb = (L + BLOCK - 1) // BLOCK
+    Lpad = nb * BLOCK
+    Rd = (lambda t: t.to(store_dtype).double()) if emulate_rounding else (lambda t: t)
+    K = torch.cat([t.double() for t in kv_pyramid(k)], dim=2)
+    V = torch.cat([t.double() for t in kv_pyramid(v)], dim=2)
+    K[:, :, L:Lpad] = 0.0
+    V[:, :, L:Lpad] = 0.0
+    key_level = torch.cat([torch.full((Lpad // p,), p, dtype=torch.int64) for p in LEVELS])
+    key_block = torch.cat([torch.arange(Lpad // p) // (BLOCK // p) for p in LEVELS])
+    bias = key_level.double().log()
+    dead = torch.zeros_like(key_level, dtype=torch.bool)
+    if not ref_tail:
+        dead[L:Lpad] = True
+    qf, of, dof = q.double(), out.double(), dout.double()
+    lse = lse.double()
+    live = torch.isfinite(lse)
+    lse_s = torch.where(live, lse, torch.zeros_like(lse))
+    m64 = mask.to(torch.int64)
+    dq = torch.zeros(B, H, L, D, dtype=torch.float64)
+    dK = torch.zeros_like(K)
+    dV = torch.zeros_like(V)
+    for i in range(nb):
+        r0, r1 = i * BLOCK, min(L, (i + 1) * BLOCK)
+        keep = (m64[:, :, i, :][:, :, key_block] == key_level) & ~dead          # [B,H,R]
+        cols = keep.flatten(0, 1).any(0).nonzero().squeeze(1)   # keys live in any (b, h): the rest add 0
+        if cols.numel() == 0:
+            continue
+        Kc, Vc = K[:, :, cols], V[:, :, cols]
+        s = torch.matmul(qf[:, :, r0:r1], Kc.transpose(-1, -2)) * scale + bias[cols]
+        s = s.masked_fill(~keep[:, :, None, cols], float("-inf"))
+        p = torch.exp(s - lse_s[:, :, r0:r1, None]) * live[:, :, r0:r1, None]
+        do = dof[:, :, r0:r1]
+        delta = (do * of[:, :, r0:r1]).sum(-1, keepdim=True)
+        ds = Rd(p * (torch.matmul(do, Vc.transpose(-1, -2)) - delta))
+        p = Rd(p)
+        dq[:, :, r0:r1] = torch.matmul(ds, Kc) * scale
+        dK[:, :, cols] += torch.matmul(ds.transpose(-1, -2), qf[:, :, r0:r1]) * scale
+        dV[:, :, cols] += torch.matmul(p.transpose(-1, -2), do)
+    dk = torch.zeros(B, H, L, D, dtype=torch.float64)
+    dv = torch.zeros(B, H, L, D, dtype=torch.float64)
+    off = 0
+    rows = torch.arange(L)
+    for p_, w in zip(LEVELS, fold_weights):
+        dk += dK[:, :, off + rows // p_] * w
+        dv += dV[:, :, off + rows // p_] * w
+        off += Lpad // p_
+    if emulate_rounding:
+        dq, dk, dv = (t.to(store_dtype) for t in (dq, dk, dv))
+    return dq.float(), dk.float(), dv.float()
+
+
 def density(ratios=None) -> float:
     """adaptive_block_sparse_attn's reported density (TRI/cogvideo_newattn.py:227-231)."""
     ratios = ML_MASK_RATIOS if ratios is None else ratios

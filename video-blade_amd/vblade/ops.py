@@ -769,19 +769,32 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
 
 
 def ml_attention_bwd(dout, q, kpyr, vpyr, level_mask_u8, out, lse, *, rows=None, scale=None,
-                     ref_tail=True, heavy_rows=2, kernel_select: int = 0, kernels_ran: Optional[list] = None):
+                     ref_tail=True, heavy_rows=2, kernel_select: int = 0, kernels_ran: Optional[list] = None,
+                     grads=None, workspace_bytes: Optional[list] = None):
     """vb_ml_attn_bwd: gradients of the multi-level attention. q/out/dout [B,H,L,D] (rows through
     ``rows``), pyramids and mask as the forward; lse as ml_attention_fwd(want_lse=True) wrote it.
     Returns (dq, dk, dv) [B,H,L,D] in q's dtype (dk/dv at the caller's rows). ``kernel_select`` /
-    ``kernels_ran`` as attention_bwd (VB_BWD_SEL_DQ_RING4 is refused here)."""
+    ``kernels_ran`` as attention_bwd (VB_BWD_SEL_DQ_RING4 is refused here). ``grads``: (dq, dk, dv)
+    buffers of the caller, [B,H,L,D] in q's dtype on q's device, any strides the kernels accept
+    (unit d-stride, the others multiples of 8 elements, 16-byte aligned); they are fully
+    overwritten and returned. ``workspace_bytes`` (a list) receives the size
+    vb_ml_attn_bwd_workspace_size reported for the call."""
     dev = _require_gpu(dout, q, kpyr, vpyr, level_mask_u8, out, lse, rows)
     q, out, dout = _aligned_bhld(q), _aligned_bhld(out), _aligned_bhld(dout)
     B, H, L, D = q.shape
     m = level_mask_u8 if level_mask_u8.stride(-1) == 1 else level_mask_u8.contiguous()
     lse = lse.float().contiguous()
-    dq = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
-    dk = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
-    dv = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+    if grads is None:
+        dq = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+        dk = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+        dv = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+    else:
+        dq, dk, dv = grads
+        for name, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+            _check_dev(f"ml_attention_bwd: grads {name}", t, dev)
+            if tuple(t.shape) != (B, H, L, D) or t.dtype != q.dtype:
+                raise ValueError(f"ml_attention_bwd: grads {name} must be [{B},{H},{L},{D}] {q.dtype}, got "
+                                 f"{tuple(t.shape)} {t.dtype}")
     a = MlBwdArgs()
     a.q, a.q_stride, a.rows = q.data_ptr(), _s3(q), _ptr(rows)
     a.kpyr, a.vpyr = kpyr.data_ptr(), vpyr.data_ptr()
@@ -801,6 +814,8 @@ def ml_attention_bwd(dout, q, kpyr, vpyr, level_mask_u8, out, lse, *, rows=None,
     a.kernels_ran = ctypes.pointer(ran)
     lib = _lib.load()
     nbytes = int(lib.vb_ml_attn_bwd_workspace_size(ctypes.byref(a)))
+    if workspace_bytes is not None:
+        workspace_bytes.append(nbytes)
     ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     check(lib.vb_ml_attn_bwd(ctypes.byref(a), _stream(dev)), "vb_ml_attn_bwd")
