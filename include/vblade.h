@@ -224,6 +224,53 @@ int vb_mask_predict(const vb_predict_args* args, void* stream);   /* nb <= 320 (
  * with num_keep 64. */
 int vb_mask_predict_long(const vb_predict_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The whole mask rule of transfer_attn_to_mask (cogvideo_blocksparseattn.py:177-249;
+ * wanx_blocksparseattn.py:162-233): mode="energy" with bounds and threshold per (batch, head) (the
+ * CogVideoX copy's [B,H] max_retain_ratio / min_retain_ratio tensors, :230-231), and mode="topk"
+ * (:205-225). Per q-block row of nc scores, rounded to the storage dtype T and ranked in descending
+ * order (ties: lower column first); cum[i] = the fp32 running sum of the sorted values, each prefix
+ * rounded to T; total = cum[nc-1].
+ *   VB_RULE_ENERGY  the rule of vb_mask_predict / vb_energy_mask with min_keep[b,h], max_keep[b,h]
+ *                   and energy_threshold[b,h]; a NULL array takes the scalar of the call.
+ *   VB_RULE_TOPK    k0 = init_k_bh[b,h] (or the scalar init_k); e = cum[k0-1];
+ *                   c_lo = e >= T(total * grow_below), c_hi = e >= T(total * shrink_below);
+ *                   k = k0; if (!c_lo && k0 < nr) k = min(3k, nr);
+ *                   if (!c_hi && k0 < nr) k = min(k/3*2, nr)  (on the updated k, integer division);
+ *                   the k best columns are kept (k may be 0), then the forced tail as in energy
+ *                   mode. In vb_block_mask_rule k is also capped at nc. min_keep, max_keep and
+ *                   energy_threshold are unused.
+ * A scalar init_k outside [1, nc] is VB_ERR_INVALID before any launch. Values read from DEVICE
+ * arrays (init_k_bh, min_keep, max_keep) cannot be checked on the host without a synchronisation:
+ * the kernel clamps each to [1, nc] before any use as an index or a bound (for the energy rule the
+ * clamp never changes the mask a scalar call with the same value writes).
+ * ------------------------------------------------------------------------------------------ */
+enum vb_rule_mode { VB_RULE_ENERGY = 0, VB_RULE_TOPK = 1 };
+typedef struct vb_mask_rule {
+  int mode;
+  const int32_t* min_keep;          /* device [B,H] or NULL: the scalar of the call */
+  const int32_t* max_keep;
+  const float*   energy_threshold;
+  int            init_k;            /* top-k: scalar k0 ... */
+  const int32_t* init_k_bh;         /* ... or device [B,H] (wins when non-NULL) */
+  float          grow_below, shrink_below;   /* <= 0: 0.6 / 0.9, the reference's constants */
+} vb_mask_rule;
+
+/* vb_mask_predict with the rule above applied by the score kernel's epilogue (no second launch, no
+ * re-read of po); any nb in [1, 1024]; every other option of the call works as without a rule, and
+ * po and the pooled / pyramid outputs are the same bits. mask_count and mask_rows_kept count the
+ * kept blocks (forced ones included) in both modes. rule == NULL: the call and the bits of
+ * vb_mask_predict (nb <= 320) / vb_mask_predict_long. mask_level != 0 with a rule: VB_ERR_INVALID. */
+int vb_mask_predict_rule(const vb_predict_args* args, const vb_mask_rule* rule, void* stream);
+
+/* The rule alone on given scores (vb_energy_mask's sibling): po [B,H,nr,nc] contiguous storage dtype
+ * -> mask [B,H,nr,nc], nc <= 1024. energy_threshold / min_keep / max_keep are the scalars that NULL
+ * arrays of an energy-mode rule fall back to. rows_kept (nullable): int32 [B,H,nr], kept blocks per
+ * mask row. rule == NULL: vb_energy_mask. */
+int vb_block_mask_rule(const void* po, int B, int H, int nr, int nc, const vb_mask_rule* rule,
+                       float energy_threshold, int min_keep, int max_keep, int force_tail, int dtype,
+                       uint8_t* mask, unsigned long long* mask_count, int32_t* rows_kept, void* stream);
+
 /* random_sample_tokens' index draw (cogvideo_blocksparseattn.py:45-46): the caller draws the
  * uniforms (torch.rand(B,H,1,block), q first then k, so the RNG stream is the reference's); this
  * replaces the two topk(num_keep) calls: rand_q/rand_k fp32 [rows, n] -> q_off/k_off int32

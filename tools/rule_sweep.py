@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Mask-rule sweep of the adaptive module on the CogVideoX and Wan headline shapes, in ONE process on
+ONE GPU, on bench.py's locality-faithful inputs (local_qkv). Timing as tools/keep_sweep.py: the
+settings interleaved round by round, 5 calls between an event pair, the median over the rounds; a
+second default module gives the A/A spread.
+
+Settings: the default energy rule (scalar bounds: vb_mask_predict), the same rule with its bounds as
+uniform per-head arrays (vb_mask_predict_rule: what the rule instantiation itself costs), top-k mode
+at init_k 0.05 / 0.1 / 0.2, and one per-head budget set (the odd heads at half the default
+max_retain_ratio). Per setting: the predictor's launches as the module issues them (pooled K/V pass
+riding), the whole module call and its ratio to the default, the kept-block fraction, and the PSNR
+of the module output against dense SDPA on the same inputs.
+
+usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--out FILE.json]
+       rocprofv3 --kernel-trace --stats -d DIR -- python tools/rule_sweep.py --variant cog --one-call SETTING
+       (four module calls of one setting and nothing else: a kernel trace then shows its launches
+       per call, tools/kstats.py DIR)"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "video-blade_amd"))
+sys.path.insert(0, ROOT)
+import vblade  # noqa: E402
+from vblade import ops  # noqa: E402
+from vblade.attention import VARIANT_DEFAULTS  # noqa: E402
+from bench import local_qkv  # noqa: E402
+
+SEED = 1234
+INIT_KS = (0.05, 0.1, 0.2)
+
+
+def psnr(x, ref):
+    mse = torch.mean((x.double() - ref.double()) ** 2).item()
+    peak = ref.double().abs().max().item()
+    return 99.0 if mse == 0 else 10 * math.log10(peak * peak / mse)
+
+
+def timed(fn, reps=5):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def settings(variant, H):
+    d = VARIANT_DEFAULTS[variant]
+    mk = lambda **kw: vblade.AdaptiveBlockSparseAttn(variant, log_every=0, **kw)  # noqa: E731
+    mods = {"energy": mk(), "energy#aa": mk()}
+    mods["energy/uniform[H]"] = mk(max_retain_ratio=torch.full((H,), d["max_retain_ratio"]),
+                                   min_retain_ratio=torch.full((H,), d["min_retain_ratio"]),
+                                   energy_threshold=torch.full((H,), 0.95))
+    for ik in INIT_KS:
+        mods[f"topk/{ik}"] = mk(mask_mode="topk", init_k=ik)
+    half = torch.full((H,), d["max_retain_ratio"])
+    half[1::2] *= 0.5
+    mods["energy/odd heads at half max"] = mk(max_retain_ratio=half)
+    return mods
+
+
+def sweep(variant, rounds, dev):
+    H, D = (48, 64) if variant == "cog" else (12, 128)
+    q, k, v = local_qkv(variant, H, D, 0, dev)
+    L = q.shape[2]
+    mods = settings(variant, H)
+    dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
+    res = {}
+
+    def fns(m):
+        copies = not (m._gather(D) and m._rows(dev) is not None)
+        outs = ops.pool_kv_outputs(k, m.sample_gap, reordered=copies)
+
+        def pred():
+            torch.cuda.manual_seed(SEED)
+            return m.predict_mask(q, k, pool=(v, m.sample_gap, outs))
+
+        def call():
+            torch.cuda.manual_seed(SEED)
+            return m(q, k, v)
+        return {"pred_fused_ms": pred, "call_ms": call}
+
+    with torch.no_grad():
+        work = {lab: fns(m) for lab, m in mods.items()}
+        for lab, m in mods.items():   # warm up; quality figures from this call
+            out = work[lab]["call_ms"]()
+            torch.cuda.synchronize()
+            res[lab] = {"kept_fraction": m.last_mask.float().mean().item(), "psnr_vs_dense_db": psnr(out, dense)}
+            work[lab]["pred_fused_ms"]()
+        times = {lab: {f: [] for f in work[lab]} for lab in mods}
+        for _ in range(rounds):
+            for f in ("pred_fused_ms", "call_ms"):
+                for lab in mods:
+                    times[lab][f].append(timed(work[lab][f]))
+    for lab in mods:
+        for f, ts in times[lab].items():
+            res[lab][f] = statistics.median(ts)
+            res[lab][f + "_min"] = min(ts)
+            res[lab][f.replace("_ms", "_vs_energy")] = res[lab][f] / statistics.median(times["energy"][f])
+    return {"variant": variant, "B": 1, "H": H, "L": L, "D": D, "nb": (L + 127) // 128,
+            "inputs": "bench.local_qkv(seed 0)", "rounds": rounds, "calls_per_round": 5, "settings": res}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", default="both")
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--one-call", default=None, metavar="SETTING")
+    a = ap.parse_args()
+    dev = torch.device("cuda")
+    if a.one_call:
+        variant = "cog" if a.variant == "both" else a.variant
+        H, D = (48, 64) if variant == "cog" else (12, 128)
+        m = settings(variant, H)[a.one_call]
+        q, k, v = local_qkv(variant, H, D, 0, dev)
+        with torch.no_grad():
+            for _ in range(4):
+                m(q, k, v)
+        torch.cuda.synchronize()
+        print(f"{variant} {a.one_call}: 4 calls, kept {m.last_mask.float().mean().item():.4f}")
+        return
+    out = {"device": torch.cuda.get_device_name(0), "results": []}
+    for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
+        r = sweep(variant, a.rounds, dev)
+        out["results"].append(r)
+        print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks)")
+        print("  setting                      | fused pred ms (x energy) | call ms (x energy) | kept   | PSNR dB")
+        for lab, d in r["settings"].items():
+            print(f"  {lab:<28} | {d['pred_fused_ms']:.4f} ({d['pred_fused_vs_energy']:.3f}) | "
+                  f"{d['call_ms']:.4f} ({d['call_vs_energy']:.3f}) | {d['kept_fraction']:.4f} | "
+                  f"{d['psnr_vs_dense_db']:.2f}", flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -12,6 +12,8 @@
 //   * transfer_attn_to_mask(mode="energy") (:177-249; wanx_blocksparseattn.py:162-233): stable
 //     descending rank, fp32-accumulated cumsum rounded to the storage dtype per prefix, the first
 //     crossing of storage(total * thr), clamp to [min_keep, max_keep], forced tail rows/cols.
+//     vb_mask_predict_rule runs the rule's other forms in the same place (kRule instantiations):
+//     the energy rule with bounds and threshold per (b,h), and mode="topk" (:205-225).
 // Nothing but Po and the mask reaches HBM (R stays in LDS).
 #include <cstdlib>
 
@@ -25,6 +27,14 @@
 #include "vb_trace.hpp"
 
 namespace vb {
+
+// The kRule instantiations of the score kernel (vb_mask_predict_rule) are compiled as a translation
+// unit of their own, vb_predict_rule.hip, which includes this file with VB_PREDICT_RULE_TU set: the
+// two halves of the predictor's kernels build side by side. That unit defines launch_predict_rule
+// and nothing else with external linkage.
+#ifndef VB_PREDICT_RULE_TU
+#define VB_PREDICT_RULE_TU 0
+#endif
 
 #ifndef VB_PRED_WAVES
 #define VB_PRED_WAVES 4   // sampled q-blocks (one per wave) sharing one K stream through LDS
@@ -105,6 +115,18 @@ struct PredBands {
   int value[8], start[8], end[8];
 };
 
+// vb_mask_rule resolved by the host (vb_mask_predict_rule / vb_block_mask_rule). Read only by the
+// kRule instantiations; it sits at the END of PredParams so every other field keeps its offset.
+struct RuleParams {
+  int mode;                    // VB_RULE_ENERGY / VB_RULE_TOPK
+  int k0;                      // top-k: scalar init_k (checked on the host)
+  const int32_t* min_keep;     // device [B,H] or NULL: PredParams' scalar
+  const int32_t* max_keep;
+  const float* thr;
+  const int32_t* k0_bh;        // device [B,H] or NULL: k0
+  float lo, hi;                // top-k: grow below lo * total, shrink below hi * total
+};
+
 struct PredParams {
   const void* q; const void* k;
   int64_t qs[3], ks[3];
@@ -128,6 +150,7 @@ struct PredParams {
   unsigned long long* count;
   int32_t* rows_kept;   // [B,H,nb] kept blocks per mask row (nullable)
   int dbg;   // diagnostic builds only (VB_DEBUG_PRED): 1 = skip epilogue, 2 = skip main loop, 4 = no MFMA, 8 = no energy rule
+  RuleParams rule;   // kRule instantiations only
 };
 
 #ifndef VB_DIAG
@@ -322,6 +345,104 @@ __device__ __forceinline__ int energy_row(const float* val, uint32_t* keys, uint
     }
   }
   return energy_row_u<T, (kMaxNb + 63) / 64>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
+}
+
+// transfer_attn_to_mask(mode="topk") (cogvideo_blocksparseattn.py:205-225) on one row, as energy_row_u:
+// the same ranks and the same sequential fp32 chain over the sorted values. The rule needs the prefix
+// at position k0 - 1, anywhere in [0, nc), and the total: the chain is uniform across the wave, so
+// every lane picks the one prefix up as the chain passes it. Both conditions are evaluated at k0; the
+// second update reads the first one's result (:218-221). k0 in [1, nc] (clamped by the caller), `grow`
+// = the reference's `seq` bound of the updates (the row count), k capped at nc. Returns the kept count.
+template <class T, int U>
+__device__ __forceinline__ int topk_row_u(const float* val, uint32_t* keys, uint8_t* mrow, int nc, int k0,
+                                          int grow, float lo, float hi, int force_cols, bool force_all) {
+  const int lane = threadIdx.x & 63;
+  int rank[U];
+  row_ranks<T, U>(val, keys, nc, rank);
+  const int nc16 = (nc + 15) & ~15;
+  __builtin_amdgcn_wave_barrier();
+  float* sorted = reinterpret_cast<float*>(keys);
+  float vals[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = lane + 64 * u;
+    vals[u] = (j < nc) ? val[j] : 0.f;
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (lane + 64 * u < nc) sorted[rank[u]] = vals[u];
+  if (nc + lane < nc16) sorted[nc + lane] = 0.f;
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  const float4* s4 = reinterpret_cast<const float4*>(sorted);
+  const int at = k0 - 1;
+  float acc = 0.f, e = 0.f;
+#pragma unroll 4
+  for (int i4 = 0; i4 < nc16 / 4; ++i4) {
+    const float4 w = s4[i4];
+    const int i = 4 * i4;
+    acc += w.x; e = (i == at) ? acc : e;
+    acc += w.y; e = (i + 1 == at) ? acc : e;
+    acc += w.z; e = (i + 2 == at) ? acc : e;
+    acc += w.w; e = (i + 3 == at) ? acc : e;   // padding past nc adds zeros
+  }
+  const float total = round_to<T>(acc);   // cum_energy[..., -1]
+  e = round_to<T>(e);                     // cum_energy[..., k0 - 1]
+  const bool c_lo = e >= round_to<T>(total * lo), c_hi = e >= round_to<T>(total * hi);
+  int k = k0;
+  if (!c_lo && k0 < grow) k = min(3 * k, grow);
+  if (!c_hi && k0 < grow) k = min((k / 3) * 2, grow);
+  k = min(k, nc);
+  int kept = 0;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = lane + 64 * u;
+    if (j < nc) {
+      const bool keep = force_all || rank[u] < k || j >= nc - force_cols;
+      mrow[j] = keep ? 1 : 0;
+      kept += keep;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o);
+  return kept;
+}
+// rows of up to kMaxNbLong columns (the rule instantiations are long ones)
+template <class T>
+__device__ __forceinline__ int topk_row(const float* val, uint32_t* keys, uint8_t* mrow, int nc, int k0, int grow,
+                                        float lo, float hi, int force_cols, bool force_all) {
+  switch ((nc + 63) >> 6) {
+    case 1: return topk_row_u<T, 1>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 2: return topk_row_u<T, 2>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 3: return topk_row_u<T, 3>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 4: return topk_row_u<T, 4>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 5: return topk_row_u<T, 5>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 6: return topk_row_u<T, 6>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 7: return topk_row_u<T, 7>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 8: return topk_row_u<T, 8>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 9: case 10: return topk_row_u<T, 10>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 11: case 12: return topk_row_u<T, 12>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    case 13: case 14: return topk_row_u<T, 14>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+    default: return topk_row_u<T, (kMaxNbLong + 63) / 64>(val, keys, mrow, nc, k0, grow, lo, hi, force_cols, force_all);
+  }
+}
+
+// One row under a vb_mask_rule: head bh's values are read here, once per row (bh is uniform, so these
+// are scalar loads), and every value that comes from a device array is clamped to [1, nc] before it
+// is used as an index or a bound. The scalars were checked on the host.
+template <class T>
+__device__ __forceinline__ int rule_row(const RuleParams& r, int bh, const float* val, uint32_t* keys, uint8_t* mrow,
+                                        int nc, int grow, float thr, int min_keep, int max_keep, int force_cols,
+                                        bool force_all) {
+  if (r.mode == VB_RULE_TOPK) {
+    const int k0 = r.k0_bh ? min(max(r.k0_bh[bh], 1), nc) : r.k0;
+    return topk_row<T>(val, keys, mrow, nc, k0, grow, r.lo, r.hi, force_cols, force_all);
+  }
+  if (r.min_keep) min_keep = min(max(r.min_keep[bh], 1), nc);
+  if (r.max_keep) max_keep = min(max(r.max_keep[bh], 1), nc);
+  if (r.thr) thr = r.thr[bh];
+  return energy_row<T, true>(val, keys, mrow, nc, thr, min_keep, max_keep, force_cols, force_all);
 }
 
 // Multi-level rank bands (transfer_attn_to_mask, Triton/cogvideo_newattn.py:154-207; vb_level_mask's
@@ -526,8 +647,11 @@ __global__ void __launch_bounds__(256) sample_rows_kernel(const PredParams p) {
 //     lanes 0-31 the first key block's row maximum and lanes 32-63 the second's; R is
 //     [q-block][key block][16 rows]; a wave runs the epilogue of its two q-blocks in turn.
 // The wave's unit of work is therefore a 32-row *group* of the sampled q stream (`qbs`, `ng` of them).
-template <int D, class T, bool kEnergy, bool kLong = false, int kKeep = 32>
+// kRule: the instantiations behind vb_mask_predict_rule (long ones). Only the last step of the epilogue
+// differs: rule_row (per-head bounds, top-k mode) instead of energy_row with the call's scalars.
+template <int D, class T, bool kEnergy, bool kLong = false, int kKeep = 32, bool kRule = false>
 __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_predict_kernel(const PredParams p) {
+  static_assert(!kRule || kLong, "the rule instantiations are long ones");
   static_assert(kKeep == 16 || kKeep == 32 || kKeep == 64, "sampling densities: 16, 32 or 64 tokens per block");
   static_assert(kKeep == 32 || (kQPW<D> == 1 && VB_PRED_GATHER), "densities 16 and 64: one group per wave, gather mode");
   constexpr int KS = D / 16;
@@ -996,7 +1120,11 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
       return;
     }
     const bool force_all = p.force_tail > 0 && qb >= nb - p.force_tail;
-    const int kept = energy_row<T, kLong>(val, keys, mrow, nb, p.thr, p.min_keep, p.max_keep, p.force_tail, force_all);
+    int kept;
+    if constexpr (kRule)
+      kept = rule_row<T>(p.rule, bh, val, keys, mrow, nb, nb, p.thr, p.min_keep, p.max_keep, p.force_tail, force_all);
+    else
+      kept = energy_row<T, kLong>(val, keys, mrow, nb, p.thr, p.min_keep, p.max_keep, p.force_tail, force_all);
     if (p.count && lane == 0) atomicAdd(p.count, (unsigned long long)kept);
     if (p.rows_kept && lane == 0) p.rows_kept[(int64_t)bh * nb + qb] = kept;
   };
@@ -1019,6 +1147,7 @@ __global__ void __launch_bounds__(kPThreads, VB_PRED_MIN_WG) VB_PRED_OCC mask_pr
 // random_sample_tokens' topk (cogvideo_blocksparseattn.py:45-46): for every row of `n` uniform draws,
 // the indices of the `keep` largest values in descending order of value (ties -> lower index
 // first). One wave per row; blockIdx.y selects the q or the k draws.
+#if !VB_PREDICT_RULE_TU
 __global__ void __launch_bounds__(256) topk_offsets_kernel(const float* rq, const float* rk, int rows, int n,
                                                            int keep, int32_t* oq, int32_t* ok) {
   __shared__ alignas(16) float buf[4][256];
@@ -1027,6 +1156,7 @@ __global__ void __launch_bounds__(256) topk_offsets_kernel(const float* rq, cons
   if (row >= rows || n > 256) return;
   topk_wave((blockIdx.y ? rk : rq) + (int64_t)row * n, n, keep, (blockIdx.y ? ok : oq) + (int64_t)row * keep, buf[wave]);
 }
+#endif
 
 // LDS floats per row buffer of energy_mask_kernel (val and keys each; keys padded to 16)
 __host__ __device__ inline int energy_row_floats(int nc) { return nc <= kMaxNb ? kEnergyRow : ((nc + 15) & ~15); }
@@ -1053,6 +1183,51 @@ __global__ void __launch_bounds__(256) energy_mask_kernel(const void* po, int ro
   const int kept = energy_row<T, true>(val, reinterpret_cast<uint32_t*>(val + erow), mask + (int64_t)row * nc, nc,
                                        thr, min_keep, max_keep, force_tail, force_all);
   if (count && lane == 0) atomicAdd(count, (unsigned long long)kept);
+}
+
+// vb_block_mask_rule: energy_mask_kernel with rule_row in place of energy_row (one wave per row; the
+// row's head is row / nr). `grow` of the top-k updates is the row count nr.
+template <class T>
+__global__ void __launch_bounds__(256) rule_mask_kernel(const void* po, int rows_total, int nc, const RuleParams rule,
+                                                        float thr, int min_keep, int max_keep, int force_tail, int nr,
+                                                        uint8_t* mask, unsigned long long* count, int32_t* rows_kept) {
+  extern __shared__ __attribute__((aligned(16))) float energy_buf[];
+  const int erow = energy_row_floats(nc);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows_total) return;
+  const typename T::raw* src = reinterpret_cast<const typename T::raw*>(po) + (int64_t)row * nc;
+  float* val = energy_buf + wave * 2 * erow;
+  for (int j = lane; j < nc; j += 64) val[j] = T::to_f32(src[j]);
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_wave_barrier();
+  const int i = row % nr;
+  const bool force_all = force_tail > 0 && i >= nr - force_tail;
+  const int kept = rule_row<T>(rule, row / nr, val, reinterpret_cast<uint32_t*>(val + erow), mask + (int64_t)row * nc,
+                               nc, nr, thr, min_keep, max_keep, force_tail, force_all);
+  if (count && lane == 0) atomicAdd(count, (unsigned long long)kept);
+  if (rows_kept && lane == 0) rows_kept[row] = kept;
+}
+
+// vb_mask_rule -> RuleParams; nc = the row width a scalar init_k is checked against
+static int resolve_rule(const vb_mask_rule* r, int nc, int min_keep, int max_keep, const std::string& fn, RuleParams* out) {
+  if (r->mode != VB_RULE_ENERGY && r->mode != VB_RULE_TOPK)
+    return fail(VB_ERR_INVALID, fn + "unknown rule mode " + std::to_string(r->mode));
+  RuleParams p{};
+  p.mode = r->mode;
+  if (r->mode == VB_RULE_TOPK) {
+    if (!r->init_k_bh && (r->init_k < 1 || r->init_k > nc))
+      return fail(VB_ERR_INVALID, fn + "init_k must be in [1, " + std::to_string(nc) + "], got " + std::to_string(r->init_k));
+    p.k0 = r->init_k; p.k0_bh = r->init_k_bh;
+    p.lo = r->grow_below > 0.f ? r->grow_below : 0.6f;
+    p.hi = r->shrink_below > 0.f ? r->shrink_below : 0.9f;
+  } else {
+    if ((!r->min_keep && min_keep < 1) || (!r->max_keep && max_keep < 1))
+      return fail(VB_ERR_INVALID, fn + "keep counts must be >= 1");
+    p.min_keep = r->min_keep; p.max_keep = r->max_keep; p.thr = r->energy_threshold;
+  }
+  *out = p;
+  return 0;
 }
 
 static size_t predict_smem_bytes(int nb, int D, bool long_rows) {
@@ -1091,10 +1266,10 @@ static int64_t philox_x_only_numel() {
   return n;
 }
 
-template <int D, class T, bool kLong, int kKeep = 32>
+template <int D, class T, bool kLong, int kKeep = 32, bool kRule = false>
 static int launch_predict(const PredParams& p, hipStream_t stream, hipEvent_t staged) {
   const size_t smem = predict_smem_bytes(p.nb, D, kLong);
-  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY, kLong, kKeep>;
+  auto kern = mask_predict_kernel<D, T, !VB_PRED_SPLIT_ENERGY, kLong, kKeep, kRule>;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)smem) != hipSuccess)
     return fail(VB_ERR_LAUNCH, "mask_predict: cannot reserve LDS");
@@ -1116,8 +1291,25 @@ static int launch_predict(const PredParams& p, hipStream_t stream, hipEvent_t st
   return 0;
 }
 
+// the rule instantiations (long kernels, every head dim, dtype and sampling density)
+int launch_predict_rule(const PredParams& p, int dtype, int keep, hipStream_t s, hipEvent_t ev);
+#if VB_PREDICT_RULE_TU
+template <int D, class T>
+static int launch_predict_rule_dt(const PredParams& p, int keep, hipStream_t s, hipEvent_t ev) {
+  if (keep == 16) return launch_predict<D, T, true, 16, true>(p, s, ev);
+  if (keep == 64) return launch_predict<D, T, true, 64, true>(p, s, ev);
+  return launch_predict<D, T, true, 32, true>(p, s, ev);
+}
+int launch_predict_rule(const PredParams& p, int dtype, int keep, hipStream_t s, hipEvent_t ev) {
+  const bool bf = dtype == VB_DTYPE_BF16;
+  if (p.D == 64) return bf ? launch_predict_rule_dt<64, BF16>(p, keep, s, ev) : launch_predict_rule_dt<64, F16>(p, keep, s, ev);
+  return bf ? launch_predict_rule_dt<128, BF16>(p, keep, s, ev) : launch_predict_rule_dt<128, F16>(p, keep, s, ev);
+}
+#endif
+
 }  // namespace vb
 
+#if !VB_PREDICT_RULE_TU
 #if VB_PRED_TRACE
 VB_TRACE_GETTER(vb_debug_pred_trace, vb::g_pred_trace)
 #endif
@@ -1135,12 +1327,13 @@ extern "C" uint64_t vb_mask_predict_workspace_size(const vb_predict_args* a) {
   return vb::predict_ws_bytes(a->B, a->H, a->L, a->D, a->num_keep);
 }
 
-// vb_mask_predict and vb_mask_predict_long: one validation and parameter set-up, `fn` names the entry
-// in the messages, kLong selects the row limit and the kernel instantiation.
+// vb_mask_predict, vb_mask_predict_long and vb_mask_predict_rule: one validation and parameter
+// set-up, `fn` names the entry in the messages, kLong selects the row limit and the kernel
+// instantiation. `rule` (vb_mask_predict_rule only, kLong) selects the rule instantiations.
 template <bool kLong>
-static int mask_predict_entry(const vb_predict_args* a, void* stream) {
+static int mask_predict_entry(const vb_predict_args* a, void* stream, const vb_mask_rule* rule = nullptr) {
   using namespace vb;
-  const std::string fn = kLong ? "vb_mask_predict_long: " : "vb_mask_predict: ";
+  const std::string fn = rule ? "vb_mask_predict_rule: " : kLong ? "vb_mask_predict_long: " : "vb_mask_predict: ";
   if (!a || !a->q || !a->k || !a->q_off || !a->k_off || !a->po)
     return fail(VB_ERR_INVALID, fn + "null argument");
   if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, fn + "bad sizes");
@@ -1155,7 +1348,15 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
   // stride. Token positions are int32 throughout (sampled_row, the int32 byte-offset table, the
   // descriptors' byte counts, checked < 2^31 below), so the long entry has no such guard.
   if (!kLong && a->L > 65535) return fail(VB_ERR_UNSUPPORTED, fn + "L must be < 65536");
-  if (a->min_keep < 1 || a->max_keep < 1) return fail(VB_ERR_INVALID, fn + "keep counts must be >= 1");
+  PredParams p{};
+  if (rule) {
+    if (a->mask_level) return fail(VB_ERR_INVALID, fn + "mask_level and a rule are exclusive");
+    if (VB_PRED_SPLIT_ENERGY || !(VB_PRED_GATHER && VB_PRED_QPW64 == 1))
+      return fail(VB_ERR_UNSUPPORTED, fn + "this build variant has no rule instantiations");
+    if (int rc = resolve_rule(rule, nb, a->min_keep, a->max_keep, fn, &p.rule)) return rc;
+  } else if (a->min_keep < 1 || a->max_keep < 1) {
+    return fail(VB_ERR_INVALID, fn + "keep counts must be >= 1");
+  }
   if (a->D != 64 && a->D != 128) return fail(VB_ERR_UNSUPPORTED, fn + "head_dim must be 64 or 128");
   const uint64_t ws = predict_ws_bytes(a->B, a->H, a->L, a->D, a->num_keep);
   if (!a->workspace || a->workspace_bytes < ws || (reinterpret_cast<uintptr_t>(a->workspace) & 15))
@@ -1166,7 +1367,6 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
     return fail(VB_ERR_UNSUPPORTED, fn + "a k (b,h) slice spans >= 2 GiB");
   for (int i = 0; i < 3; ++i)
     if ((a->q_stride[i] | a->k_stride[i]) & 7) return fail(VB_ERR_INVALID, fn + "strides must be multiples of 8");
-  PredParams p{};
   p.q = a->q; p.k = a->k;
   for (int i = 0; i < 3; ++i) { p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; }
   p.rows = a->rows; p.q_off = a->q_off; p.k_off = a->k_off;
@@ -1262,6 +1462,9 @@ static int mask_predict_entry(const vb_predict_args* a, void* stream) {
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipEvent_t ev = reinterpret_cast<hipEvent_t>(a->staged_event);
   if (a->dtype != VB_DTYPE_BF16 && a->dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, fn + "unknown dtype");
+#if VB_PRED_GATHER && VB_PRED_QPW64 == 1 && !VB_PRED_SPLIT_ENERGY
+  if (rule) return launch_predict_rule(p, a->dtype, a->num_keep, s, ev);
+#endif
   if (a->num_keep != 32) {
 #if VB_PRED_GATHER && VB_PRED_QPW64 == 1
     // densities 16 and 64 exist in the long instantiation only (it writes the short one's bits for
@@ -1293,6 +1496,38 @@ extern "C" int vb_mask_predict(const vb_predict_args* a, void* stream) { return 
 
 extern "C" int vb_mask_predict_long(const vb_predict_args* a, void* stream) {
   return mask_predict_entry<true>(a, stream);
+}
+
+extern "C" int vb_mask_predict_rule(const vb_predict_args* a, const vb_mask_rule* rule, void* stream) {
+  if (rule) return mask_predict_entry<true>(a, stream, rule);
+  // no rule: the call (and the bits) of the entry that serves this row count
+  if (a && a->block > 0 && a->L > 0 && (a->L + a->block - 1) / a->block > vb::kMaxNb) return mask_predict_entry<true>(a, stream);
+  return mask_predict_entry<false>(a, stream);
+}
+
+extern "C" int vb_block_mask_rule(const void* po, int B, int H, int nr, int nc, const vb_mask_rule* rule,
+                                  float energy_threshold, int min_keep, int max_keep, int force_tail, int dtype,
+                                  uint8_t* mask, unsigned long long* mask_count, int32_t* rows_kept, void* stream) {
+  using namespace vb;
+  const std::string fn = "vb_block_mask_rule: ";
+  if (!po || !mask) return fail(VB_ERR_INVALID, fn + "null argument");
+  if (B <= 0 || H <= 0 || nr <= 0 || nc <= 0) return fail(VB_ERR_INVALID, fn + "bad sizes");
+  if (nc > kMaxNbLong) return fail(VB_ERR_UNSUPPORTED, fn + "too many columns");
+  if (force_tail < 0) return fail(VB_ERR_INVALID, fn + "force_tail must be >= 0");
+  RuleParams rp{};   // no rule: energy mode with the call's scalars (vb_energy_mask's rule)
+  vb_mask_rule none{};
+  if (int rc = resolve_rule(rule ? rule : &none, nc, min_keep, max_keep, fn, &rp)) return rc;
+  if (dtype != VB_DTYPE_BF16 && dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, fn + "unknown dtype");
+  const int rows = B * H * nr;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((rows + 3) / 4);
+  if (dtype == VB_DTYPE_BF16)
+    hipLaunchKernelGGL(rule_mask_kernel<BF16>, grid, dim3(256), energy_smem_bytes(nc), s, po, rows, nc, rp, energy_threshold,
+                       min_keep, max_keep, force_tail, nr, mask, mask_count, rows_kept);
+  else
+    hipLaunchKernelGGL(rule_mask_kernel<F16>, grid, dim3(256), energy_smem_bytes(nc), s, po, rows, nc, rp, energy_threshold,
+                       min_keep, max_keep, force_tail, nr, mask, mask_count, rows_kept);
+  return check_launch("rule_mask_kernel");
 }
 
 extern "C" int vb_energy_mask(const void* po, int B, int H, int nr, int nc, float energy_threshold, int min_keep,
@@ -1327,3 +1562,4 @@ extern "C" int vb_sample_offsets(const float* rand_q, const float* rand_k, int r
                      rand_q, rand_k, rows, n, keep, q_off, k_off);
   return check_launch("topk_offsets_kernel");
 }
+#endif   // !VB_PREDICT_RULE_TU

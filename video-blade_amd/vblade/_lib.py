@@ -67,6 +67,19 @@ class PredictArgs(ctypes.Structure):
     ]
 
 
+VB_RULE_ENERGY, VB_RULE_TOPK = 0, 1
+
+
+class MaskRule(ctypes.Structure):
+    """vb_mask_rule (include/vblade.h)."""
+    _fields_ = [
+        ("mode", ctypes.c_int),
+        ("min_keep", _vp), ("max_keep", _vp), ("energy_threshold", _vp),
+        ("init_k", ctypes.c_int), ("init_k_bh", _vp),
+        ("grow_below", ctypes.c_float), ("shrink_below", ctypes.c_float),
+    ]
+
+
 class BwdArgs(ctypes.Structure):
     """vb_attn_bwd_args (include/vblade.h)."""
     _fields_ = [
@@ -156,6 +169,10 @@ SIGNATURES = {
     "vb_mask_predict_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(PredictArgs)]),
     "vb_mask_predict": (ctypes.c_int, [ctypes.POINTER(PredictArgs), _vp]),
     "vb_mask_predict_long": (ctypes.c_int, [ctypes.POINTER(PredictArgs), _vp]),
+    "vb_mask_predict_rule": (ctypes.c_int, [ctypes.POINTER(PredictArgs), ctypes.POINTER(MaskRule), _vp]),
+    "vb_block_mask_rule": (ctypes.c_int, [
+        _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(MaskRule),
+        ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "vb_sample_offsets": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "vb_energy_mask": (ctypes.c_int, [
         _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,

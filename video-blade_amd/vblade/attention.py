@@ -132,6 +132,16 @@ class AdaptiveBlockSparseAttn(nn.Module):
     its own predicted mask, Block-Sparse-Attention's renumbering of the ones) or "shared_head0"
     (every head attends with head 0's mask). The sparsity statistic counts the predicted mask in
     both modes, as the reference's (:394) does.
+    mask_mode: transfer_attn_to_mask's ``mode``: "energy" (default) or "topk" (:205-225): every row
+    starts from the budget ``init_k`` (a ratio of the row's blocks below 1, int(nb * init_k), or a
+    block count, as the reference reads it) and triples it / shrinks it to k/3*2 when those blocks
+    hold less than 0.6 / 0.9 of the row's energy; the retain ratios and the threshold are unused.
+    min_retain_ratio, max_retain_ratio, energy_threshold: a float, or a tensor [H] or [B,H] with one
+    value per head (the CogVideoX reference's [B,H] ratio tensors, :230-231, :347-348). Tensor
+    ratios become per-head block counts on the device (``retain_counts``' arithmetic per variant),
+    once per (tensor, B, H, nb, device); a steady-state call launches nothing extra and never
+    synchronises. Either option runs the mask rule in the predictor's own launch
+    (vb_mask_predict_rule); without them the module makes the calls it always made.
     """
 
     def __init__(self, variant: str = "cog", *, combine: str = "fused", **overrides):
@@ -140,7 +150,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
             raise ValueError(f"variant must be one of {list(VARIANT_DEFAULTS)}")
         cfg = dict(VARIANT_DEFAULTS[variant])
         unknown = set(overrides) - set(cfg) - {"energy_threshold", "block", "num_keep", "overlap", "gather_kv",
-                                               "mask_head_mode", "order", "order_window", "persistent"}
+                                               "mask_head_mode", "order", "order_window", "persistent",
+                                               "mask_mode", "init_k"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
@@ -152,7 +163,15 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self.sample_gap = int(cfg["sample_gap"])
         self.text_length = int(cfg["text_length"])
         self.force_tail = int(cfg["force_tail"])
-        self.energy_threshold = float(cfg.get("energy_threshold", 0.95))
+        thr = cfg.get("energy_threshold", 0.95)
+        self.energy_threshold = thr if isinstance(thr, torch.Tensor) else float(thr)
+        self.mask_mode = cfg.get("mask_mode", "energy")
+        if self.mask_mode not in ops.RULE_MODES:
+            raise ValueError(f"mask_mode must be one of {list(ops.RULE_MODES)}, got {self.mask_mode!r}")
+        self.init_k = cfg.get("init_k")
+        if self.mask_mode == "topk" and (self.init_k is None or not self.init_k > 0):
+            raise ValueError("mask_mode='topk' needs init_k > 0 (a ratio below 1 or a block count)")
+        self._per_head_cache = {}
         self.block = int(cfg.get("block", 128))
         self.num_keep = int(cfg.get("num_keep", 32))
         if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
@@ -245,6 +264,44 @@ class AdaptiveBlockSparseAttn(nn.Module):
         for g=15 in bf16. The training path's combine rounds it the same way (vb_pool.hip)."""
         return float(torch.log(torch.tensor(float(self.sample_gap), dtype=dtype)).item())
 
+    def _per_head(self, name, value, B, H, nb, device):
+        """[B,H] device tensor of a per-head option given as a tensor [H] or [B,H]: kept-block
+        counts (int32) of a retain ratio, by ``retain_counts``' arithmetic on the device (cog:
+        clamp((nb * fp32 ratio).to(int32), min=1), cogvideo_blocksparseattn.py:230-231; wan: the
+        same in float64, the Python float of wanx :215-216), or the fp32 thresholds. Built once per
+        (tensor, B, H, nb, device) and cached, so a steady-state call launches nothing for it."""
+        key = (name, B, H, nb, str(device))
+        hit = self._per_head_cache.get(key)
+        if hit is not None and hit[0] is value and hit[1] == value._version:
+            return hit[2]
+        if value.dim() not in (1, 2) or value.shape[-1] != H or (value.dim() == 2 and value.shape[0] != B):
+            raise ValueError(f"{name} must be a float or a tensor [H] or [B,H] = [{B},{H}], "
+                             f"got {tuple(value.shape)}")
+        v = value.detach().to(device)
+        if name == "energy_threshold":
+            out = v.float()
+        else:
+            v = v.float() if self.variant == "cog" else v.double()
+            out = torch.clamp((nb * v).to(torch.int32), min=1)
+        out = out.expand(B, H).contiguous()
+        self._per_head_cache[key] = (value, value._version, out)
+        return out
+
+    def _mask_rule(self, B, H, nb, device):
+        """The ops.MaskRule of a call, or None when the options are the scalar energy rule's."""
+        if self.mask_mode == "topk":
+            k0 = int(nb * self.init_k) if self.init_k < 1 else int(self.init_k)
+            return ops.MaskRule(mode="topk", init_k=k0)
+        per_head = {n: v for n, v in (("min_keep", self.min_retain_ratio), ("max_keep", self.max_retain_ratio),
+                                      ("energy_threshold", self.energy_threshold))
+                    if isinstance(v, torch.Tensor)}
+        if not per_head:
+            return None
+        names = {"min_keep": "min_retain_ratio", "max_keep": "max_retain_ratio",
+                 "energy_threshold": "energy_threshold"}
+        return ops.MaskRule(mode="energy", **{n: self._per_head(names[n], v, B, H, nb, device)
+                                              for n, v in per_head.items()})
+
     # -------------------------------------------------------------------------------- forward
     def predict_mask(self, q, k, q_off=None, k_off=None, count=None, staged_event=None, pool=None,
                      rows_kept=None):
@@ -264,6 +321,17 @@ class AdaptiveBlockSparseAttn(nn.Module):
         elif k_off is None:
             k_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
         nb = (L + self.block - 1) // self.block
+        rule = self._mask_rule(B, H, nb, q.device)
+        if rule is not None:
+            # scalars of the options given as tensors are placeholders the rule's arrays replace
+            thr = 0.95 if isinstance(self.energy_threshold, torch.Tensor) else self.energy_threshold
+            lo, hi = retain_counts(nb, 1.0 if isinstance(self.min_retain_ratio, torch.Tensor) else self.min_retain_ratio,
+                                   1.0 if isinstance(self.max_retain_ratio, torch.Tensor) else self.max_retain_ratio,
+                                   self.variant)
+            return ops.mask_predict(q, k, q_off, k_off, rows=self._rows(q.device), energy_threshold=thr,
+                                    min_keep=lo, max_keep=hi, force_tail=self.force_tail, mask_count=count,
+                                    staged_event=staged_event, rand=rand, philox=philox, pool=pool,
+                                    rows_kept=rows_kept, num_keep=self.num_keep, rule=rule)
         lo, hi = retain_counts(nb, self.min_retain_ratio, self.max_retain_ratio, self.variant)
         po, mask = ops.mask_predict(q, k, q_off, k_off, rows=self._rows(q.device),
                                     energy_threshold=self.energy_threshold, min_keep=lo,

@@ -6,9 +6,10 @@ computed by libvblade_hip.so. Calls on CPU tensors raise (there is no CPU fallba
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 import os
-from typing import Optional
+from typing import Optional, Union
 
 import numpy as np
 import torch
@@ -357,10 +358,74 @@ def block_sparse_attn_bwd(dout, q_unpad, k_unpad, v_unpad, out_unpad, softmax_ls
 # ----------------------------------------------------------------------------------------------
 # mask predictor, energy rule, pooling, combine
 # ----------------------------------------------------------------------------------------------
+RULE_MODES = {"energy": _lib.VB_RULE_ENERGY, "topk": _lib.VB_RULE_TOPK}
+
+
+@dataclasses.dataclass
+class MaskRule:
+    """vb_mask_rule: the mask rule of a mask_predict / block_mask_rule call.
+
+    mode "energy": ``min_keep``, ``max_keep`` (kept-block counts) and ``energy_threshold`` each an
+    int / float, an int32 / float32 device tensor [B,H] (one value per head), or None (the call's
+    own scalar argument). mode "topk": ``init_k`` is the starting count k0, an int in [1, nc] or an
+    int32 device tensor [B,H]; ``grow_below`` / ``shrink_below`` are the energy fractions (0 = the
+    reference's 0.6 / 0.9) below which a row's budget triples / shrinks to k/3*2. Values in device
+    tensors are clamped to [1, nc] by the kernel (they cannot be checked without a sync)."""
+    mode: str = "energy"
+    init_k: Union[int, torch.Tensor, None] = None
+    min_keep: Union[int, torch.Tensor, None] = None
+    max_keep: Union[int, torch.Tensor, None] = None
+    energy_threshold: Union[float, torch.Tensor, None] = None
+    grow_below: float = 0.0
+    shrink_below: float = 0.0
+
+
+def _rule_args(rule, B, H, dev, energy_threshold, min_keep, max_keep):
+    """(ctypes MaskRule, tensors to keep alive, energy_threshold, min_keep, max_keep scalars)."""
+    if isinstance(rule, dict):
+        rule = MaskRule(**rule)
+    if rule.mode not in RULE_MODES:
+        raise ValueError(f"mask rule mode must be one of {list(RULE_MODES)}, got {rule.mode!r}")
+    r = _lib.MaskRule()
+    r.mode = RULE_MODES[rule.mode]
+    keep = []
+
+    def per_head(name, v, dtype):
+        if v.numel() != B * H or tuple(v.shape) != (B, H):
+            raise ValueError(f"mask rule: {name} must be a [B,H] = [{B},{H}] tensor, got {tuple(v.shape)}")
+        _check_dev(f"mask rule: {name}", v, dev)
+        v = v.to(dtype).contiguous()
+        keep.append(v)
+        return v.data_ptr()
+
+    if rule.mode == "topk":
+        if rule.init_k is None:
+            raise ValueError("mask rule: mode 'topk' needs init_k")
+        if isinstance(rule.init_k, torch.Tensor):
+            r.init_k_bh = per_head("init_k", rule.init_k, torch.int32)
+        else:
+            r.init_k = int(rule.init_k)
+        r.grow_below, r.shrink_below = float(rule.grow_below), float(rule.shrink_below)
+    else:
+        if isinstance(rule.min_keep, torch.Tensor):
+            r.min_keep = per_head("min_keep", rule.min_keep, torch.int32)
+        elif rule.min_keep is not None:
+            min_keep = rule.min_keep
+        if isinstance(rule.max_keep, torch.Tensor):
+            r.max_keep = per_head("max_keep", rule.max_keep, torch.int32)
+        elif rule.max_keep is not None:
+            max_keep = rule.max_keep
+        if isinstance(rule.energy_threshold, torch.Tensor):
+            r.energy_threshold = per_head("energy_threshold", rule.energy_threshold, torch.float32)
+        elif rule.energy_threshold is not None:
+            energy_threshold = rule.energy_threshold
+    return r, keep, float(energy_threshold), int(min_keep), int(max_keep)
+
+
 def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.95, min_keep=1,
                  max_keep=1, force_tail=0, scale=None, mask_count=None, want_mask=True,
                  staged_event=None, rand=None, philox=None, pool=None, pyr=None, level=None,
-                 rows_kept=None, long_rows=False, num_keep=None):
+                 rows_kept=None, long_rows=False, num_keep=None, rule=None):
     """vb_mask_predict. q,k [B,H,L,D]; q_off/k_off int32 [B,H,num_keep]. Returns (po, mask) with
     po [B,H,nb,nb] in q.dtype and mask uint8 [B,H,nb,nb] (None with want_mask=False: the scores
     only, no energy rule). ``staged_event`` (a torch.cuda.Event) is recorded once the sampled
@@ -385,13 +450,17 @@ def mask_predict(q, k, q_off=None, k_off=None, *, rows=None, energy_threshold=0.
     ``philox=`` it is the width of the offsets drawn (default 32; the draws stay [B,H,1,block]);
     with given offsets the width is read from q_off.shape[-1], which k_off and an explicit
     ``num_keep`` must match (ValueError otherwise). The library refuses other widths
-    (VB_ERR_UNSUPPORTED)."""
+    (VB_ERR_UNSUPPORTED).
+    ``rule``: a MaskRule (or a dict of its fields): the call goes to vb_mask_predict_rule, whose
+    epilogue applies that rule (per-head energy bounds, or the top-k mode) instead of the scalar
+    energy rule; any nb up to MAX_BLOCKS_LONG, ``long_rows`` is not needed. None: the calls made
+    without it."""
     try:
         return _mask_predict(q, k, q_off, k_off, rows=rows, energy_threshold=energy_threshold,
                              min_keep=min_keep, max_keep=max_keep, force_tail=force_tail, scale=scale,
                              mask_count=mask_count, want_mask=want_mask, staged_event=staged_event,
                              rand=rand, philox=philox, pool=pool, pyr=pyr, level=level,
-                             rows_kept=rows_kept, long_rows=long_rows, num_keep=num_keep)
+                             rows_kept=rows_kept, long_rows=long_rows, num_keep=num_keep, rule=rule)
     except Exception as e:
         # the claimed draws go back to the generator only when nothing was launched: a Python-side
         # error (validation, or a host-side VBladeError such as the library failing to load, code
@@ -426,7 +495,7 @@ def _offset_width(q_off, k_off, num_keep, drawn: bool) -> int:
 
 def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_keep, force_tail,
                   scale, mask_count, want_mask, staged_event, rand, philox, pool, pyr, level, rows_kept,
-                  long_rows=False, num_keep=None):
+                  long_rows=False, num_keep=None, rule=None):
     keep = _offset_width(q_off, k_off, num_keep, drawn=rand is not None or philox is not None)
     if k.shape != q.shape:
         raise ValueError(f"mask_predict: k and v must have q's shape {tuple(q.shape)}, "
@@ -449,6 +518,12 @@ def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_k
         k_off = torch.empty(B, H, keep, device=dev, dtype=torch.int32)
     q_off = q_off.to(torch.int32).contiguous()
     k_off = k_off.to(torch.int32).contiguous()
+    rule_c = None
+    if rule is not None:
+        if level is not None:
+            raise ValueError("mask_predict: rule and level are exclusive")
+        rule_c, rule_keep, energy_threshold, min_keep, max_keep = _rule_args(
+            rule, B, H, dev, energy_threshold, min_keep, max_keep)
     a = PredictArgs()
     a.q, a.k = q.data_ptr(), k.data_ptr()
     a.q_stride, a.k_stride = _s3(q), _s3(k)
@@ -506,7 +581,10 @@ def _mask_predict(q, k, q_off, k_off, *, rows, energy_threshold, min_keep, max_k
             raise ValueError("mask_predict: rows_kept must be contiguous int32 [B,H,nb]")
         _check_dev("mask_predict: rows_kept", rows_kept, dev)
         a.mask_rows_kept = rows_kept.data_ptr()
-    if long_rows:
+    if rule_c is not None:
+        check(lib.vb_mask_predict_rule(ctypes.byref(a), ctypes.byref(rule_c), _stream(dev)),
+              "vb_mask_predict_rule")
+    elif long_rows:
         check(lib.vb_mask_predict_long(ctypes.byref(a), _stream(dev)), "vb_mask_predict_long")
     else:
         check(lib.vb_mask_predict(ctypes.byref(a), _stream(dev)), "vb_mask_predict")
@@ -592,6 +670,31 @@ def energy_mask(po, *, energy_threshold=0.95, min_keep=1, max_keep=1, force_tail
                                      int(min_keep), int(max_keep), int(force_tail),
                                      _dtype_code(po), mask.data_ptr(), _ptr(mask_count),
                                      _stream(dev)), "vb_energy_mask")
+    return mask
+
+
+def block_mask_rule(po, rule=None, *, energy_threshold=0.95, min_keep=1, max_keep=1, force_tail=0,
+                    mask_count=None, rows_kept=None):
+    """vb_block_mask_rule: a MaskRule (or a dict of its fields; None = the scalar energy rule) alone
+    on scores po [B,H,nr,nc] (bf16/fp16, nc <= 1024) -> uint8 mask. ``rows_kept`` (contiguous int32
+    [B,H,nr]) receives the kept blocks per mask row, ``mask_count`` an atomic add of their sum."""
+    dev = _require_gpu(po, rows_kept, mask_count)
+    po = po.contiguous()
+    B, H, nr, nc = po.shape
+    rule_c = None
+    if rule is not None:
+        rule_c, rule_keep, energy_threshold, min_keep, max_keep = _rule_args(
+            rule, B, H, dev, energy_threshold, min_keep, max_keep)
+    if rows_kept is not None and (rows_kept.dtype != torch.int32 or rows_kept.numel() != B * H * nr
+                                  or not rows_kept.is_contiguous()):
+        raise ValueError("block_mask_rule: rows_kept must be contiguous int32 [B,H,nr]")
+    mask = torch.empty(B, H, nr, nc, device=dev, dtype=torch.uint8)
+    check(_lib.load().vb_block_mask_rule(po.data_ptr(), B, H, nr, nc,
+                                         ctypes.byref(rule_c) if rule_c is not None else None,
+                                         float(energy_threshold), int(min_keep), int(max_keep),
+                                         int(force_tail), _dtype_code(po), mask.data_ptr(),
+                                         _ptr(mask_count), _ptr(rows_kept), _stream(dev)),
+          "vb_block_mask_rule")
     return mask
 
 
