@@ -134,6 +134,47 @@ def test_mask_predict_matches_oracle_at_density(case, dtype, keep):
     assert cnt.item() == int(ref_mask.sum())
 
 
+# (D, dtype, keep, rule): the score-kernel instantiations (16 of vb_mask_predict / _long, 12 of
+# vb_mask_predict_rule) that no other GPU test launches; rule=False cases go through the long entry
+_OTHERWISE_UNLAUNCHED = [
+    (64, torch.float16, 32, False), (128, torch.float16, 32, False),
+    (128, torch.float16, 16, False), (128, torch.float16, 64, False),
+    (64, torch.float16, 16, True), (64, torch.float16, 32, True), (64, torch.float16, 64, True),
+    (128, torch.bfloat16, 16, True), (128, torch.bfloat16, 64, True),
+    (128, torch.float16, 16, True), (128, torch.float16, 64, True),
+]
+
+
+@pytest.mark.parametrize("D,dtype,keep,rule", _OTHERWISE_UNLAUNCHED)
+def test_remaining_score_kernel_instantiations(D, dtype, keep, rule):
+    """B=1, H=2, L=300: three blocks (an odd count), the last one partial. Scores and mask bit for bit
+    against the oracle; at density 32 also against the short entry's call."""
+    ops = _ops()
+    B, H, L = 1, 2, 300
+    q = _exact_inputs(B, H, L, D, 1).to(dtype)
+    k = _exact_inputs(B, H, L, D, 2).to(dtype)
+    g = torch.Generator().manual_seed(7)
+    qo, ko = _offsets(B, H, keep, g)
+    perm = torch.randperm(L, generator=g)
+    lo, hi, ft = 1, 2, 1
+    kw = dict(rows=perm.int().to(DEV), min_keep=lo, max_keep=hi, force_tail=ft)
+    args = (q.to(DEV), k.to(DEV), qo.int().to(DEV), ko.int().to(DEV))
+    if rule:   # the energy rule's scalars given through a rule: the rule instantiation
+        po, mask = ops.mask_predict(*args, rule=ops.MaskRule(), **kw)
+    else:
+        po, mask = ops.mask_predict(*args, long_rows=True, **kw)
+    qs = O.sample_tokens(O.pad_replicate(q[:, :, perm], 128), qo)
+    ks = O.sample_tokens(O.pad_replicate(k[:, :, perm], 128), ko)
+    ref_po = O.pooled_scores(qs, ks, 1.0 / D ** 0.5, keep, dtype)
+    po_c = po.float().cpu()
+    print(f"D {D} {dtype} keep {keep} rule {rule}: exact share {(po_c == ref_po).float().mean().item():.6f}")
+    assert torch.equal(po_c, ref_po)
+    assert torch.equal(mask.bool().cpu(), O.energy_mask(po_c, lo, hi, 0.95, ft, dtype))
+    if keep == 32:
+        po_s, mask_s = ops.mask_predict(*args, **kw)
+        assert torch.equal(po, po_s) and torch.equal(mask, mask_s)
+
+
 # ------------------------------------------------------------------------- 2. in-launch offsets
 def _case_b_gpu(keep, seed=11):
     variant, L, D, H, _ = CASES["b"]

@@ -2,7 +2,7 @@
 // cogvideox/train/special_attentions_local/TrainRelated/cogvideo_blocksparseattn.py:83-88), fused
 // with the Gilbert-ordered K/V copies (the reference's index_select, :148-150). Shared by the
 // stand-alone pool_kv_kernel (vb_pool.hip) and the pooling workgroups of the mask predictor's launch
-// (vb_predict.hip), which run it beside the score kernel without a second stream.
+// (vb_predict_kernel.hpp), which run it beside the score kernel without a second stream.
 #pragma once
 #include "vb_common.hpp"
 

@@ -1,7 +1,7 @@
 // KV pyramid of the multi-level path (the reference kernel's _forward, kernels/
 // block_sparse_attn_kernel_with_backward_9_10.py:1311-1320: k_2/k_4/k_8 via pad_to_multiple
 // :1239-1250 and pooling :1252-1270). Shared by the stand-alone kv_pyramid_kernel (vb_ml.hip) and
-// the pyramid workgroups of the mask predictor's launch (vb_predict.hip).
+// the pyramid workgroups of the mask predictor's launch (vb_predict_kernel.hpp).
 #pragma once
 #include "vb_common.hpp"
 
