@@ -466,6 +466,57 @@ typedef struct vb_ml_attn_bwd_args {
 uint64_t vb_ml_attn_bwd_workspace_size(const vb_ml_attn_bwd_args* args);
 int vb_ml_attn_bwd(const vb_ml_attn_bwd_args* args, void* stream);
 
+/* ==========================================================================================
+ * The attention processors' q/k prologue in one pass: the q/k norm and RoPE that sit between the
+ * projections and inner_attention (cogvideox/train/modify_cogvideo.py:54-64, a per-head LayerNorm
+ * then apply_rotary_emb on the video rows; wanx/train/modify_wan.py:99-116, an RMSNorm over the
+ * projection row then the float64 complex RoPE). Every element is read once and written once.
+ *
+ * A tensor is [B,L,H,D] as the projection wrote it: element (b,l,h,d) at base + b*stride[0] +
+ * l*stride[1] + h*D + d (strides in ELEMENTS, multiples of 8, row stride >= H*D; 16-byte aligned
+ * bases) — the memory whose [B,H,L,D] view the attention kernels take through their strides.
+ * `out` may equal `x` (in place); any other overlap is undefined. D = 64 or 128, H*D <= 8192
+ * (8128 with the RMSNorm).
+ *
+ * Per row, in the eager chain's order and with its rounding points:
+ *   norm  VB_QK_NORM_LAYER_HEAD  LayerNorm over each head's D elements: fp32 mean, then fp32 mean of
+ *                                the squared deviations (two-pass), (x-mean)*rsqrt(var+eps)*weight+bias
+ *         VB_QK_NORM_RMS_ROW     RMSNorm over the H*D row: x*rsqrt(mean(x^2)+eps)*weight
+ *         weight (nullable = 1) and bias (nullable = 0; LayerNorm only) hold D (LayerNorm) or H*D
+ *         (RMSNorm) values of the storage dtype or, with affine_f32 != 0, fp32. The result is
+ *         rounded to the storage dtype; RoPE works on the rounded value.
+ *   rope  VB_QK_ROPE_REAL        rows l >= rope_start: y = x*cos[l-rope_start] + rot(x)*sin[l-rope_start]
+ *                                with rot(x)[2i] = -x[2i+1], rot(x)[2i+1] = x[2i]; cos/sin fp32
+ *                                [L-rope_start, D]; two fp32 products and one fp32 sum, each rounded
+ *                                (never fused), then the storage dtype. Rows below rope_start get
+ *                                the norm alone.
+ *         VB_QK_ROPE_COMPLEX     every row (rope_start must be 0): pairs (a,b) = (x[2i], x[2i+1])
+ *                                times freqs[l][i] = (c,s) in fp64, (a*c - b*s, a*s + b*c), rounded
+ *                                double -> float -> storage dtype; freqs [L, D/2] (re,im) pairs of
+ *                                fp32 or, with freqs_f64 != 0, fp64.
+ * No trigonometry runs on the device: the tables are the caller's.
+ * ========================================================================================== */
+enum vb_qk_norm { VB_QK_NORM_NONE = 0, VB_QK_NORM_LAYER_HEAD = 1, VB_QK_NORM_RMS_ROW = 2 };
+enum vb_qk_rope { VB_QK_ROPE_NONE = 0, VB_QK_ROPE_REAL = 1, VB_QK_ROPE_COMPLEX = 2 };
+typedef struct vb_qk_prologue_args {
+  const void* x; void* out;
+  int64_t x_stride[2]; int64_t out_stride[2];   /* batch, row */
+  int B, L, H, D;
+  int dtype;
+  int norm;                 /* vb_qk_norm */
+  const void* weight; const void* bias;
+  int affine_f32;           /* weight and bias are fp32 (else the storage dtype) */
+  float eps;
+  int rope;                 /* vb_qk_rope */
+  int rope_start;
+  const float* cos; const float* sin;
+  const void* freqs; int freqs_f64;
+} vb_qk_prologue_args;
+/* q and, when k != NULL, k (same B, L, H, D and dtype as q; its own modes and buffers) in ONE launch:
+ * a workgroup takes whole token rows of both, so tensors that name the same RoPE table with the same
+ * mode and rope_start read each table row once. */
+int vb_qk_prologue(const vb_qk_prologue_args* q, const vb_qk_prologue_args* k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,13 +34,13 @@ int check_launch(const char* what) {
 
 // Persistent launches: the occupancy of `kernel` at `smem` bytes of dynamic LDS times the device's
 // CUs, rounded down to a multiple of 8 (every XCD the same number of workgroups). Host queries only,
-// cached per (kernel, device, LDS size).
+// cached per (kernel, device, workgroup size, LDS size).
 int resident_grid(const void* kernel, int threads, size_t smem) {
   static std::mutex mu;
-  static std::map<std::tuple<const void*, int, size_t>, int> cache;
+  static std::map<std::tuple<const void*, int, int, size_t>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  const auto key = std::make_tuple(kernel, dev, smem);
+  const auto key = std::make_tuple(kernel, dev, threads, smem);
   {
     std::lock_guard<std::mutex> g(mu);
     auto it = cache.find(key);

@@ -147,6 +147,25 @@ class MlBwdArgs(ctypes.Structure):
     ]
 
 
+class QkPrologueArgs(ctypes.Structure):
+    """vb_qk_prologue_args (include/vblade.h)."""
+    _fields_ = [
+        ("x", _vp), ("out", _vp),
+        ("x_stride", ctypes.c_int64 * 2), ("out_stride", ctypes.c_int64 * 2),
+        ("B", ctypes.c_int), ("L", ctypes.c_int), ("H", ctypes.c_int), ("D", ctypes.c_int),
+        ("dtype", ctypes.c_int),
+        ("norm", ctypes.c_int),
+        ("weight", _vp), ("bias", _vp),
+        ("affine_f32", ctypes.c_int), ("eps", ctypes.c_float),
+        ("rope", ctypes.c_int), ("rope_start", ctypes.c_int),
+        ("cos", _vp), ("sin", _vp),
+        ("freqs", _vp), ("freqs_f64", ctypes.c_int),
+    ]
+
+
+VB_QK_NORM_NONE, VB_QK_NORM_LAYER_HEAD, VB_QK_NORM_RMS_ROW = 0, 1, 2
+VB_QK_ROPE_NONE, VB_QK_ROPE_REAL, VB_QK_ROPE_COMPLEX = 0, 1, 2
+
 # vb_attn_bwd_args.kernel_select / kernels_ran bits (include/vblade.h)
 VB_BWD_SEL_DKDV_ROUND3, VB_BWD_SEL_DQ_ROUND3, VB_BWD_SEL_DQ_RING4 = 1, 2, 4
 VB_BWD_RAN_DKDV_PIPE, VB_BWD_RAN_DKDV_ROUND3 = 1, 2
@@ -201,6 +220,7 @@ SIGNATURES = {
     "vb_lse_combine": (ctypes.c_int, [
         _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_float, ctypes.c_int, _vp, _vp, _vp]),
+    "vb_qk_prologue": (ctypes.c_int, [ctypes.POINTER(QkPrologueArgs), ctypes.POINTER(QkPrologueArgs), _vp]),
 }
 
 _lib = None

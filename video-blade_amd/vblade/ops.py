@@ -759,6 +759,141 @@ def lse_combine(out1, lse1, out2, lse2, gap: float):
 
 
 # ----------------------------------------------------------------------------------------------
+# q/k prologue: the processors' q/k norm + RoPE in one pass (vb_qk_prologue)
+# ----------------------------------------------------------------------------------------------
+QK_NORMS = {"none": _lib.VB_QK_NORM_NONE, "layer": _lib.VB_QK_NORM_LAYER_HEAD, "rms": _lib.VB_QK_NORM_RMS_ROW}
+QK_ROPES = {"none": _lib.VB_QK_ROPE_NONE, "real": _lib.VB_QK_ROPE_REAL, "complex": _lib.VB_QK_ROPE_COMPLEX}
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _qk_affine(name, t, n, x, dev):
+    """A weight or bias of n values: the storage dtype or fp32, contiguous, 16-byte aligned."""
+    if t is None:
+        return None
+    if t.dtype not in (x.dtype, torch.float32):
+        raise TypeError(f"qk_prologue: {name} must be {x.dtype} or float32, got {t.dtype}")
+    if t.numel() != n:
+        raise ValueError(f"qk_prologue: {name} has {t.numel()} values, the norm takes {n}")
+    _check_dev(f"qk_prologue: {name}", t, dev)
+    t = t.detach().reshape(n).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _qk_table(name, t, shape, dev):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"qk_prologue: {name} must be {tuple(shape)}, got {tuple(t.shape)}")
+    t = t.detach().to(dev).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def qk_prologue(q_proj: torch.Tensor, k_proj: Optional[torch.Tensor] = None, *, heads: int,
+                norm="none", q_weight=None, q_bias=None, q_eps: float = 1e-5,
+                k_weight=None, k_bias=None, k_eps: Optional[float] = None,
+                rope="none", rope_start: int = 0, cos=None, sin=None, freqs=None,
+                inplace: bool = False):
+    """vb_qk_prologue: the attention processors' q/k norm and RoPE in one pass over q and k.
+
+    q_proj / k_proj: the projections' outputs, [B,L,heads*D] or [B,L,heads,D] (rows contiguous).
+    ``norm``: "none", "layer" (LayerNorm over each head's D values; weight/bias of D values) or "rms"
+    (RMSNorm over the heads*D row; weight of heads*D values); ``rope``: "none", "real" (cos/sin fp32
+    [L-rope_start, D] on the rows from ``rope_start``) or "complex" (``freqs``: a complex64/128
+    tensor of L*D/2 values, every row). A (q, k) pair gives each tensor its own mode, e.g.
+    ``rope=("real", "none")`` for cross attention. Weights are the storage dtype or fp32.
+    ``inplace`` overwrites the projections. Returns the [B,heads,L,D] view(s) the attention kernels
+    take — no transpose copy — as q or (q, k). Rounding points: include/vblade.h."""
+    norms, ropes = _pair(norm), _pair(rope)
+    for m in norms:
+        if m not in QK_NORMS:
+            raise ValueError(f"qk_prologue: norm must be one of {sorted(QK_NORMS)}, got {m!r}")
+    for m in ropes:
+        if m not in QK_ROPES:
+            raise ValueError(f"qk_prologue: rope must be one of {sorted(QK_ROPES)}, got {m!r}")
+    W = q_proj.shape[-1] if q_proj.dim() == 3 else heads * q_proj.shape[-1]
+    if q_proj.dim() not in (3, 4) or W % heads or (q_proj.dim() == 4 and q_proj.shape[2] != heads):
+        raise ValueError(f"qk_prologue: expected [B,L,{heads}*D] or [B,L,{heads},D], got {tuple(q_proj.shape)}")
+    dev = _require_gpu(q_proj, k_proj)
+    if k_proj is not None and (k_proj.shape != q_proj.shape or k_proj.dtype != q_proj.dtype):
+        raise ValueError("qk_prologue: k_proj must have q_proj's shape and dtype")
+    B, L = q_proj.shape[:2]
+    D = W // heads
+    table = {}
+    if "real" in ropes:
+        if cos is None or sin is None:
+            raise ValueError("qk_prologue: rope='real' needs cos and sin")
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+            raise TypeError("qk_prologue: cos and sin must be float32")
+        if not 0 <= rope_start <= L:
+            raise ValueError(f"qk_prologue: rope_start {rope_start} outside [0, {L}]")
+        table["cos"] = _qk_table("cos", cos, (L - rope_start, D), dev)
+        table["sin"] = _qk_table("sin", sin, (L - rope_start, D), dev)
+        if rope_start == L:   # no row takes it, and an empty table has no address to hand over
+            ropes = tuple("none" if m == "real" else m for m in ropes)
+    if "complex" in ropes:
+        if freqs is None or not freqs.is_complex() or freqs.dtype not in (torch.complex64, torch.complex128):
+            raise TypeError("qk_prologue: rope='complex' needs freqs as a complex64 or complex128 tensor")
+        if freqs.numel() != L * (D // 2) or freqs.shape[-1] != D // 2:
+            raise ValueError(f"qk_prologue: freqs must hold [{L}, {D // 2}] values, got {tuple(freqs.shape)}")
+        table["freqs"] = _qk_table("freqs", torch.view_as_real(freqs.reshape(L, D // 2)), (L, D // 2, 2), dev)
+
+    keep = []   # tensors the launch reads stay alive until it is enqueued
+
+    def fill(x, mode, rmode, w, b, eps):
+        x3 = x.reshape(B, L, W) if x.dim() == 4 else x   # a view for rows-contiguous inputs
+        ok = (x3.stride(2) == 1 and (B == 1 or x3.stride(0) % 8 == 0) and x3.stride(1) % 8 == 0 and x3.stride(1) >= W
+              and x3.data_ptr() % 16 == 0)
+        if inplace:
+            if not ok or x3.data_ptr() != x.data_ptr():
+                raise ValueError("qk_prologue: inplace needs 16-byte aligned rows with strides that are multiples of 8")
+            out = x3
+        else:
+            if not ok:
+                x3 = x3.contiguous()
+            out = torch.empty(B, L, W, device=dev, dtype=x.dtype)
+        a = _lib.QkPrologueArgs()
+        a.x, a.out = x3.data_ptr(), out.data_ptr()
+        a.x_stride = (ctypes.c_int64 * 2)(x3.stride(0) if B > 1 else 0, x3.stride(1))
+        a.out_stride = (ctypes.c_int64 * 2)(out.stride(0) if B > 1 else 0, out.stride(1))
+        a.B, a.L, a.H, a.D = B, L, heads, D
+        a.dtype = _dtype_code(x)
+        a.norm = QK_NORMS[mode]
+        if mode == "none" and (w is not None or b is not None):
+            raise ValueError("qk_prologue: weight/bias given without a norm")
+        if mode == "rms" and b is not None:
+            raise ValueError("qk_prologue: the RMSNorm takes no bias")
+        n = D if mode == "layer" else W
+        w, b = _qk_affine("weight", w, n, x, dev), _qk_affine("bias", b, n, x, dev)
+        if w is not None and b is not None and w.dtype != b.dtype:
+            raise TypeError("qk_prologue: weight and bias must share a dtype")
+        a.weight, a.bias = _ptr(w), _ptr(b)
+        a.affine_f32 = int(any(t is not None and t.dtype == torch.float32 for t in (w, b)))
+        a.eps = float(eps)
+        a.rope = QK_ROPES[rmode]
+        if rmode == "real":
+            a.rope_start = int(rope_start)
+            a.cos, a.sin = table["cos"].data_ptr(), table["sin"].data_ptr()
+        elif rmode == "complex":
+            a.freqs = table["freqs"].data_ptr()
+            a.freqs_f64 = int(table["freqs"].dtype == torch.float64)
+        keep.extend((x3, w, b))
+        return a, out
+
+    qa, q_out = fill(q_proj, norms[0], ropes[0], q_weight, q_bias, q_eps)
+    ka = k_out = None
+    if k_proj is not None:
+        ka, k_out = fill(k_proj, norms[1], ropes[1], k_weight, k_bias, q_eps if k_eps is None else k_eps)
+    check(_lib.load().vb_qk_prologue(ctypes.byref(qa), ctypes.byref(ka) if ka is not None else None,
+                                     _stream(dev)), "vb_qk_prologue")
+    del keep
+    q_view = q_out.view(B, L, heads, D).transpose(1, 2)
+    if k_proj is None:
+        return q_view
+    return q_view, k_out.view(B, L, heads, D).transpose(1, 2)
+
+
+# ----------------------------------------------------------------------------------------------
 # multi-level path (Triton/cogvideo_newattn.py + kernels/block_sparse_attn_kernel_with_backward_9_10.py)
 # ----------------------------------------------------------------------------------------------
 # Triton/cogvideo_newattn.py:12-18
