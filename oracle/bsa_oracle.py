@@ -233,6 +233,115 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return out, lse
 
 
+def union_keys(q, k, v, block_mask, kp=None, vp=None, kp_log_bias=0.0, use_main=True, block=128):
+    """The one key set the fused forward's softmax runs over: the main keys a row's mask row keeps
+    (``block_mask`` None = all of them; ``use_main`` False = none) followed by the pooled keys.
+    Returns (K [B,H,n,D], V [B,H,n,D], visible bool [B,H,Lq,n], bias fp64 [n] in natural-log
+    units: 0 for main keys, ``kp_log_bias`` for pooled ones), K/V in the inputs' dtype."""
+    B, H, Lq, D = q.shape
+    nbq = (Lq + block - 1) // block
+    Ks, Vs, vis, bias = [], [], [], []
+    if use_main:
+        Lk = k.shape[2]
+        if block_mask is None:
+            keep = torch.ones(B, H, Lq, Lk, dtype=torch.bool)
+        else:
+            nbk = (Lk + block - 1) // block
+            m = block_mask.bool().expand(B, H, *block_mask.shape[2:])[:, :, :nbq, :nbk]
+            keep = m[:, :, torch.arange(Lq) // block][:, :, :, torch.arange(Lk) // block]
+        Ks.append(k), Vs.append(v), vis.append(keep), bias.append(torch.zeros(Lk, dtype=torch.float64))
+    if kp is not None:
+        Lkp = kp.shape[2]
+        Ks.append(kp), Vs.append(vp), vis.append(torch.ones(B, H, Lq, Lkp, dtype=torch.bool))
+        bias.append(torch.full((Lkp,), float(kp_log_bias), dtype=torch.float64))
+    return torch.cat(Ks, 2), torch.cat(Vs, 2), torch.cat(vis, 3), torch.cat(bias)
+
+
+def softmax_over_visible(q, K, V, visible, bias, scale):
+    """fp64 softmax attention of q over the keys K with per-(row, key) visibility and a per-key
+    additive logit bias (natural-log units). Rows that see no key give a zero output and -inf LSE.
+    Returns fp64 (out [B,H,Lq,D], lse [B,H,Lq])."""
+    s = torch.matmul(q.double(), K.double().transpose(-1, -2)) * scale + bias.double()
+    s = s.masked_fill(~visible, float("-inf"))
+    mx = s.amax(-1, keepdim=True)
+    mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+    p = torch.exp(s - mx)
+    l = p.sum(-1, keepdim=True)
+    out = torch.matmul(p, V.double()) / torch.where(l > 0, l, torch.ones_like(l))
+    return out, (mx + torch.log(l)).squeeze(-1)
+
+
+def joint_attention(q, k, v, mask, kp=None, vp=None, bias=0.0, sm_scale=None, use_main=True, block=128):
+    """fp64 reference of the fused forward (vb_attn_fwd): ONE softmax over the union of the kept
+    full-resolution keys and the pooled keys, the latter carrying the logit bias ``bias`` (the a9
+    identity, see adaptive_attention_joint; no intermediate rounding). ``mask`` None = dense,
+    ``kp`` None = main branch alone, ``use_main`` False = pooled keys alone (k, v ignored).
+    Returns fp64 (out [B,H,Lq,D], lse [B,H,Lq], natural log; -inf for a row with no key)."""
+    scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    K, V, vis, b = union_keys(q, k, v, mask, kp, vp, bias, use_main, block)
+    return softmax_over_visible(q, K, V, vis, b, scale)
+
+
+LOG2E_F32 = np.float32(1.4426950408889634)   # kLog2e (csrc/vb_common.hpp)
+LN2_F32 = np.float32(0.6931471805599453)     # kLn2
+
+
+def attention_fwd_emulated(q, k, v, block_mask, *, kp=None, vp=None, kp_log_bias=0.0, use_main=True,
+                           sm_scale=None, store_dtype, prescale_q=False, block=128, m_lag=None):
+    """vb_attn_fwd (csrc/vb_attn_fwd.hip) restated in fp32 with its roundings, for deriving test
+    bounds (per_row_bound): what the kernel rounds, this rounds; what it only reorders (tile order,
+    the deferred and lazy rescales, fp32 summation order) is not emulated.
+
+      * c = fp32(scale) * fp32(log2 e); pooled keys carry fp32(kp_log_bias) * fp32(log2 e) (host).
+      * training form (launches that return the LSE): scores are fp32 dot products of the storage
+        operands; the exp2 argument is fma(s, c, bias - m), one rounding.
+      * inference form (``prescale_q``; kCBias): q := storage(fp32(q) * c), and the dot product,
+        seeded with bias - m, is the exp2 argument itself.
+      * P = exp2(.) in fp32; l = sum of the fp32 P; P is rounded to the storage type as the P.V
+        operand; O accumulates in fp32; out = storage(O * (1 / l)); lse = (m + log2 l) * fp32(ln 2).
+      * m is the row's exact maximum (exp2 domain) minus ``m_lag`` (log2 units, broadcastable to
+        [B,H,Lq,1]; None = 0). The kernels' m is the maximum of the first tile processed, raised
+        later only past kRescaleSlack = 4 (training) or log2 kLazyBound (inference) log2 units, so
+        it lags the exact maximum by a data-dependent amount. The lag scales P and l alike, but it
+        decides how P rounds: with the exact maximum a row's largest P is exactly 1 and rounds
+        without error, so a row that one key owns shows the output rounding alone, while the
+        kernels round that P = 2^-lag like any other (up to 2^-9 bf16 / 2^-12 f16 of the whole row).
+        Bounds for the kernels are therefore derived with a lag whose fractional part is spread
+        over [0, 1) across the rows; which tile raises m when is not emulated.
+    Rows that see no key: zero output, -inf LSE. Returns fp32 (out, lse)."""
+    D = q.shape[-1]
+    scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(D)
+    c = np.float32(scale) * LOG2E_F32
+    K, V, vis, b = union_keys(q, k, v, block_mask, kp, vp, 0.0, use_main, block)
+    bias2 = b.float()   # exp2 domain
+    if kp is not None:
+        bias2[-kp.shape[2]:] = float(np.float32(kp_log_bias) * LOG2E_F32)
+    ninf = float("-inf")
+    if prescale_q:
+        qs = rnd(q.float() * float(c), store_dtype)
+        x = (torch.matmul(qs, K.float().transpose(-1, -2)) + bias2).masked_fill(~vis, ninf)
+        m = x.amax(-1, keepdim=True)
+        m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+        if m_lag is not None:
+            m = m - m_lag
+        x = x - m
+    else:
+        s = torch.matmul(q.float(), K.float().transpose(-1, -2))
+        m = (s * float(c) + bias2).masked_fill(~vis, ninf).amax(-1, keepdim=True)
+        m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+        if m_lag is not None:
+            m = m - m_lag
+        # fma(s, c, bias - m): the product is exact in fp64, so one rounding to fp32
+        x = (s.double() * float(c) + (bias2 - m).double()).float().masked_fill(~vis, ninf)
+    p = torch.exp2(x)
+    l = p.sum(-1, keepdim=True)
+    o = torch.matmul(rnd(p, store_dtype), V.float())
+    inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
+    out = rnd(o * inv, store_dtype)
+    lse = ((m + torch.log2(l)) * float(LN2_F32)).squeeze(-1)
+    return out, lse
+
+
 def block_sparse_attention_bwd(q, k, v, out, lse, dout, block_mask, sm_scale=None, block=128,
                                key_bias: float = 0.0, acc_dtype=torch.float64):
     """FlashAttention-2 backward semantics for a7 (LSE treated as a constant, no LSE gradient):
@@ -548,15 +657,21 @@ def two_branch_attention_bwd(q_r, k_r, v_r, kp, vp, out1, lse1, out2, lse2, alph
     return dq.float(), dk.float(), dv.float()
 
 
-def per_row_error(g: torch.Tensor, ref: torch.Tensor):
-    """Checker metric that a single wrong row cannot hide in: err[b,h,r] = ||g[b,h,r] - ref[b,h,r]||
-    / max(||ref[b,h,r]||, rms), rms = the root-mean-square row norm of ``ref`` (rows whose reference
-    is near zero are judged at the tensor's scale). Returns (worst error, (b, h, r) of that row)."""
+def per_row_errors(g: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+    """err[b,h,r] = ||g[b,h,r] - ref[b,h,r]|| / max(||ref[b,h,r]||, rms), rms = the root-mean-square
+    row norm of ``ref`` (rows whose reference is near zero are judged at the tensor's scale); a NaN
+    counts as inf. fp64 [B,H,L]."""
     g, ref = g.detach().double().cpu(), ref.detach().double().cpu()
     rn = ref.norm(dim=-1)
     rms = rn.pow(2).mean().sqrt().clamp_min(1e-300)
     err = (g - ref).norm(dim=-1) / torch.maximum(rn, rms)
-    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    return torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+
+
+def per_row_error(g: torch.Tensor, ref: torch.Tensor):
+    """Checker metric that a single wrong row cannot hide in: the worst of per_row_errors.
+    Returns (worst error, (b, h, r) of that row)."""
+    err = per_row_errors(g, ref)
     i = int(err.argmax())
     return float(err.flatten()[i]), tuple(int(x) for x in np.unravel_index(i, err.shape))
 

@@ -1,9 +1,13 @@
 """GPU parity: the HIP forward path (through the C ABI) against the oracle on the same inputs.
 
 Tolerances (bf16/fp16 inputs, fp32 accumulate; the oracle computes in fp64):
-  attention outputs   max|err| <= 2.5e-2 (bf16) / 4e-3 (fp16) on O(1) outputs,
+  attention outputs   max|err| <= 2.5e-2 (bf16) / 4e-3 (fp16). With unit-normal inputs the outputs'
+                      RMS is 0.093 at L=300, 0.054 at L=1000 and 0.038 at L=2222 (sum of w^2 ~ e/n),
+                      so these bounds are about half the signal: they catch a broken launch, not a
+                      key with a slightly wrong weight. The tight per-row bounds (from a rounding
+                      emulation, ~5e-3 bf16 / 1e-3 fp16 of the row) are in test_gpu_forward_rows.py.
                       PSNR >= 40 dB (BASELINE.json north_star)
-  LSE                 max|err| <= 2e-3 (natural log, fp32 out)
+  LSE                 max|err| <= 2e-3 (natural log, fp32 out); <= 2e-5 in test_gpu_forward_rows.py
   pooled scores / pooled K,V / combine: storage-dtype rounding of the reference reproduced;
                       differences limited to single-ulp flips from fp32 summation order.
 """
