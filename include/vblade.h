@@ -517,6 +517,59 @@ typedef struct vb_qk_prologue_args {
  * mode and rope_start read each table row once. */
 int vb_qk_prologue(const vb_qk_prologue_args* q, const vb_qk_prologue_args* k, void* stream);
 
+/* The prologue's backward, for training: dx (and the norm's parameter gradients) from the forward's
+ * input x, its modes and parameters, and g, the gradient w.r.t. the forward's output. Nothing else
+ * is saved from the forward: the statistics are recomputed from x as the forward computes them.
+ * The forward's two roundings to the storage dtype are the identity for the gradient (as autograd
+ * treats them); between loading g and storing dx everything stays in fp32 (fp64 for the complex
+ * RoPE's products), with ONE rounding to the storage dtype at the store.
+ *   RoPE^T  real     rows l >= rope_start: p = g*cos, s = g*sin, gy[2i] = p[2i] + s[2i+1],
+ *                    gy[2i+1] = p[2i+1] - s[2i]; rows below rope_start: gy = g
+ *           complex  gy = g * conj(freqs): (g_a*c + g_b*s, g_b*c - g_a*s)
+ *   norm^T  LAYER_HEAD  xhat = (x-mean)*rstd, a = gy*w: dx = rstd*(a - mean_D(a) - xhat*mean_D(a*xhat));
+ *                       dweight[d] = sum_{b,l,h} gy*xhat, dbias[d] = sum_{b,l,h} gy
+ *           RMS_ROW     xhat = x*rstd, a = gy*w: dx = rstd*(a - xhat*mean_W(a*xhat));
+ *                       dweight[c] = sum_{b,l} gy*xhat
+ *           NONE        dx = gy
+ * x: as vb_qk_prologue_args.x. g: element (b,l,h,d) at g + b*g_stride[0] + l*g_stride[1] +
+ * h*g_stride[2] + d (strides in ELEMENTS, non-negative multiples of 8, 16-byte aligned base), so
+ * [B,H,L,D]-contiguous gradients and [B,L,H,D] memory are both read where they lie. dx: storage
+ * dtype, batch and row strides like x, fully overwritten; it must not overlap x or g.
+ * dweight / dbias (each nullable): fp32 whatever the parameters' dtype, D (LAYER_HEAD) or H*D
+ * (RMS_ROW) values, fully overwritten, summed without atomics in an order that depends only on the
+ * shape and the number of workgroups: every workgroup writes its partial sums to `workspace` and a
+ * second small launch on `stream` adds them up. Both NULL (for every tensor of the call): no
+ * accumulation, no second launch, no workspace.
+ * grid_limit: 0 = the resident grid, capped at VB_QK_BWD_MAX_GRID; > 0 caps the number of
+ * workgroups. It never changes dx; equal grid_limit gives equal dweight/dbias bits.
+ * workspace: >= vb_qk_prologue_bwd_workspace_size(q, k) bytes (host arithmetic; 0 when no parameter
+ * gradient is requested), 16-byte aligned, named by the FIRST non-NULL of q and k for the whole
+ * call. The library allocates nothing and never synchronises; the call is graph-capturable. */
+#define VB_QK_BWD_MAX_GRID 1024
+typedef struct vb_qk_prologue_bwd_args {
+  const void* x; int64_t x_stride[2];           /* batch, row */
+  const void* g; int64_t g_stride[3];           /* batch, row, head */
+  void* dx; int64_t dx_stride[2];               /* batch, row */
+  float* dweight; float* dbias;
+  void* workspace; uint64_t workspace_bytes;
+  int B, L, H, D;
+  int dtype;
+  int norm;                 /* vb_qk_norm */
+  const void* weight; const void* bias;         /* bias: accepted as the forward's, never read */
+  int affine_f32;
+  float eps;
+  int rope;                 /* vb_qk_rope */
+  int rope_start;
+  const float* cos; const float* sin;
+  const void* freqs; int freqs_f64;
+  int grid_limit;
+} vb_qk_prologue_bwd_args;
+uint64_t vb_qk_prologue_bwd_workspace_size(const vb_qk_prologue_bwd_args* q, const vb_qk_prologue_bwd_args* k);
+/* Either of q and k may be NULL (a k-only backward), not both. With both, k has q's B, L, H, D,
+ * dtype and grid_limit, and one launch serves both tensors (each table row read once) unless they
+ * name two different norms or two different RoPE tables. */
+int vb_qk_prologue_bwd(const vb_qk_prologue_bwd_args* q, const vb_qk_prologue_bwd_args* k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,17 @@ processor also copies v (value.contiguous()), which the fused path hands over as
 is timed on its own line and is NOT part of the ratio.
 
   python tools/prologue_bench.py [--iters 20] [--reps 50] [--sets 3] [--warmup 5] [--out profiles/qk_prologue_ab.log]
+
+--backward times training instead: forward + backward of the eager chain under autograd against
+autograd.qk_prologue (ops.qk_prologue forward, ops.qk_prologue_bwd backward), same method, with the
+norm parameters frozen (the LoRA case: no parameter gradients) and trainable. The upstream gradients
+are [B,H,L,D]-contiguous, as ops.attention_bwd returns them, and rotate with the input sets. "GB/s"
+of the forward + backward lines is over the compulsory bytes of both passes: the forward's (above)
+plus the backward's, x and g read and dx written for q and k plus one read of the table. A third
+line times the fused backward alone (ops.qk_prologue_bwd, reduction launch included) over the
+backward's compulsory bytes: the figure to hold against the forward's fraction of the HBM peak.
+Peak memory is torch.cuda.max_memory_allocated over one call, above what was allocated before it.
+The log goes to profiles/qk_prologue_bwd_ab.log.
 """
 import argparse
 import os
@@ -39,7 +50,7 @@ SHAPES = {
 }
 
 
-def build(name, dev, dtype, sets=3):
+def build(name, dev, dtype, sets=3, backward=False):
     from vblade import ops, patch
     s = SHAPES[name]
     B, L, H, D, T = s["B"], s["L"], s["H"], s["D"], s["text"]
@@ -59,8 +70,7 @@ def build(name, dev, dtype, sets=3):
         cos, sin = ang2.cos().float(), ang2.sin().float()
         table_bytes = 2 * cos.numel() * 4
 
-        def eager():
-            qp, kp = inputs("eager")
+        def eager_chain(qp, kp):
             q = qp.view(B, -1, H, D).transpose(1, 2)
             k = kp.view(B, -1, H, D).transpose(1, 2)
             q = nq(q).to(dtype=dtype)
@@ -69,11 +79,8 @@ def build(name, dev, dtype, sets=3):
             k[:, :, T:] = patch._apply_rotary_emb_real(k[:, :, T:], (cos, sin))
             return q, k
 
-        def fused():
-            qp, kp = inputs("fused")
-            return ops.qk_prologue(qp, kp, heads=H, norm="layer", q_weight=nq.weight, q_bias=nq.bias, q_eps=nq.eps,
-                                   k_weight=nk.weight, k_bias=nk.bias, k_eps=nk.eps, rope="real", rope_start=T,
-                                   cos=cos, sin=sin)
+        fused_kw = dict(heads=H, norm="layer", q_weight=nq.weight, q_bias=nq.bias, q_eps=nq.eps,
+                        k_weight=nk.weight, k_bias=nk.bias, k_eps=nk.eps, rope="real", rope_start=T, cos=cos, sin=sin)
 
         def v_copy():
             return vp.view(B, -1, H, D).transpose(1, 2).contiguous()
@@ -86,24 +93,60 @@ def build(name, dev, dtype, sets=3):
             x_rotated = torch.view_as_complex(hs.to(torch.float64).unflatten(3, (-1, 2)))
             return torch.view_as_real(x_rotated * freqs).flatten(3, 4).type_as(hs)
 
-        def eager():
-            qp, kp = inputs("eager")
+        def eager_chain(qp, kp):
             q, k = nq(qp), nk(kp)
             q = q.unflatten(2, (H, -1)).transpose(1, 2)
             k = k.unflatten(2, (H, -1)).transpose(1, 2)
             return rope(q), rope(k)
 
-        def fused():
-            qp, kp = inputs("fused")
-            return ops.qk_prologue(qp, kp, heads=H, norm="rms", q_weight=nq.weight, q_eps=nq.eps,
-                                   k_weight=nk.weight, k_eps=nk.eps, rope="complex", freqs=freqs)
-
+        fused_kw = dict(heads=H, norm="rms", q_weight=nq.weight, q_eps=nq.eps, k_weight=nk.weight, k_eps=nk.eps,
+                        rope="complex", freqs=freqs)
         v_copy = None
+
+    def eager():
+        return eager_chain(*inputs("eager"))
+
+    def fused():
+        return ops.qk_prologue(*inputs("fused"), **fused_kw)
     with torch.no_grad():
         for n in (nq, nk):
             n.weight.add_(0.1 * torch.randn_like(n.weight))
     nbytes = 4 * B * L * H * D * vp.element_size() + table_bytes
-    return eager, fused, v_copy, nbytes
+    if not backward:
+        return eager, fused, v_copy, nbytes
+
+    # training: the same chains under autograd, each call on the next input set and its upstream gradients
+    from vblade import autograd
+    gs = [tuple((torch.randn(B, H, L, D, generator=g, device=dev)).to(dtype) for _ in range(2)) for _ in range(sets)]
+    for t in qs + ks:
+        t.requires_grad_()
+    params = [p for n in (nq, nk) for p in n.parameters()]
+    bwd_bytes = 6 * B * L * H * D * vp.element_size() + table_bytes
+
+    def set_wgrad(on):
+        for p in params:
+            p.requires_grad_(on)
+
+    def step(side, chain):
+        turn[side] += 1
+        i = turn[side] % sets
+        leaves = [qs[i], ks[i]] + [p for p in params if p.requires_grad]
+        return torch.autograd.grad(list(chain(qs[i], ks[i])), leaves, list(gs[i]))
+
+    def eager_fb():
+        return step("eager", eager_chain)
+
+    def fused_fb():
+        return step("fused", lambda qp, kp: autograd.qk_prologue(qp, kp, **fused_kw))
+
+    def fused_b():
+        turn["bwd"] = turn.get("bwd", 0) + 1
+        i = turn["bwd"] % sets
+        w = params[0].requires_grad
+        need = (w, w and name == "cog", w, w and name == "cog")
+        return ops.qk_prologue_bwd(qs[i], ks[i], gq=gs[i][0], gk=gs[i][1], need_wgrad=need, **fused_kw)
+
+    return eager_fb, fused_fb, fused_b, set_wgrad, nbytes + bwd_bytes, bwd_bytes
 
 
 def timed(fn, reps):
@@ -117,6 +160,53 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def peak_above(fn):
+    """Bytes torch.cuda.max_memory_allocated rises above the current allocation over one call of fn."""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    del out
+    return torch.cuda.max_memory_allocated() - base
+
+
+def backward_lines(args, dev, dtype):
+    lines = []
+    for name in args.shapes:
+        eager_fb, fused_fb, fused_b, set_wgrad, nbytes, bwd_bytes = build(name, dev, dtype, args.sets, backward=True)
+        s = SHAPES[name]
+        lines.append(f"{name}: q,k [{s['B']},{s['L']},{s['H']}x{s['D']}] {args.dtype}, compulsory bytes forward + backward "
+                     f"{nbytes / 1e6:.1f} MB, backward alone {bwd_bytes / 1e6:.1f} MB")
+        for wgrad in (False, True):
+            set_wgrad(wgrad)
+            for _ in range(args.warmup * args.sets):
+                e, f = eager_fb(), fused_fb()
+                fused_b()
+            torch.cuda.synchronize()
+            rel = [((a.double() - b.double()).norm() / a.double().norm()).item() for a, b in zip(e, f)]
+            del e, f
+            t = {"eager": [], "fused": [], "bwd": []}
+            for _ in range(args.iters):
+                t["eager"].append(timed(eager_fb, args.reps))
+                t["fused"].append(timed(fused_fb, args.reps))
+                t["bwd"].append(timed(fused_b, args.reps))
+            peak = {"eager": peak_above(eager_fb), "fused": peak_above(fused_fb), "bwd": peak_above(fused_b)}
+            lines.append(f" parameter gradients {'on' if wgrad else 'off (frozen norms, the LoRA case)'}; "
+                         f"||fused - eager|| / ||eager|| per gradient: " + ", ".join(f"{r:.2e}" for r in rel))
+            med = {side: statistics.median(v) for side, v in t.items()}
+            for side, label, nb in (("eager", "eager fwd+bwd", nbytes), ("fused", "fused fwd+bwd", nbytes),
+                                    ("bwd", "fused bwd alone", bwd_bytes)):
+                rate = nb / (med[side] * 1e-3)
+                lines.append(f"  {label:15s} {med[side]:8.3f} ms [{min(t[side]):.3f}, {max(t[side]):.3f}]  "
+                             f"{rate / 1e9:8.1f} GB/s  {rate / HBM_PEAK:.3f} of HBM peak  peak memory "
+                             f"{peak[side] / 1e6:8.1f} MB")
+            lines.append(f"  ratio eager/fused (fwd+bwd) {med['eager'] / med['fused']:.2f}x")
+        del eager_fb, fused_fb, fused_b, set_wgrad
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=20)
@@ -125,19 +215,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16")
     ap.add_argument("--shapes", nargs="+", choices=sorted(SHAPES), default=sorted(SHAPES))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "qk_prologue_ab.log"))
+    ap.add_argument("--backward", action="store_true", help="time forward + backward under autograd (training)")
+    ap.add_argument("--out", default=None, help="default profiles/qk_prologue_ab.log, with --backward "
+                                                "profiles/qk_prologue_bwd_ab.log")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "qk_prologue_bwd_ab.log" if args.backward else "qk_prologue_ab.log")
     if not torch.cuda.is_available():
         sys.exit("prologue_bench: needs a GPU (a CPU run says nothing about these times)")
     dev = torch.device("cuda", 0)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
-    lines = [f"# tools/prologue_bench.py --iters {args.iters} --reps {args.reps} --sets {args.sets} --warmup {args.warmup} --dtype {args.dtype}",
+    lines = [f"# tools/prologue_bench.py{' --backward' if args.backward else ''} --iters {args.iters} --reps {args.reps} --sets {args.sets} --warmup {args.warmup} --dtype {args.dtype}",
              f"# device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; ms per call, median [min, max] of "
              f"{args.iters} windows of {args.reps} back-to-back calls over {args.sets} input sets, eager and fused "
              f"alternating; per-call figures, not a kernel trace; "
              f"HBM peak {HBM_PEAK / 1e12:.1f} TB/s"]
+    if args.backward:
+        lines += backward_lines(args, dev, dtype)
     with torch.no_grad():
-        for name in args.shapes:
+        for name in ([] if args.backward else args.shapes):
             eager, fused, v_copy, nbytes = build(name, dev, dtype, args.sets)
             for _ in range(args.warmup * args.sets):   # both sides on the same set each time
                 e, f = eager(), fused()

@@ -20,10 +20,11 @@
 // the norm are written out as fmaf, so the listing holds exactly the FMAs the source names.
 #include <cmath>
 
-#include "vb_common.hpp"
+#include "vb_qk_prologue.hpp"
 
 namespace vb {
 namespace {
+using namespace qk;
 
 struct QkTensor {
   const uint8_t* x; uint8_t* out;
@@ -35,67 +36,9 @@ struct QkTensor {
 struct QkTask {
   QkTensor t[2];
   int nt;            // 1: q alone, 2: q and k
-  int rope_start;    // the launch's one RoPE table: both tensors read the row once
-  const float* cos; const float* sin;
-  const void* freqs; int freqs_f64;
+  RopeSrc rope;      // the launch's one RoPE table: both tensors read the row once
   int B, L, H, D;
 };
-
-constexpr int kMaxWaves = 16;
-
-template <class T>
-__device__ __forceinline__ void unpack8(const u32x4 r, float (&f)[8]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[2 * e] = T::bits_to_f32(r[e] & 0xffff);
-    f[2 * e + 1] = T::bits_to_f32(r[e] >> 16);
-  }
-}
-
-// element i of a weight or bias (storage dtype or fp32); `fill` when the array is absent
-template <class T>
-__device__ __forceinline__ float affine_at(const void* p, int f32, int i, float fill) {
-  if (!p) return fill;
-  return f32 ? reinterpret_cast<const float*>(p)[i] : T::bits_to_f32(reinterpret_cast<const uint16_t*>(p)[i]);
-}
-
-__device__ __forceinline__ void lds8(const float* p, float (&f)[8]) {
-  const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { f[e] = a[e]; f[4 + e] = b[e]; }
-}
-
-// the RoPE table entries of one lane's 8 elements: (cos, sin) per element, or (re, im) per pair
-struct RopeTab {
-  float c[8], s[8];
-  double zr[4], zi[4];
-};
-
-template <int ROPE>
-__device__ __forceinline__ void load_tab(const QkTask& t, int l, int D, int d0, RopeTab& tab) {
-  if (ROPE == VB_QK_ROPE_REAL) {
-    // rows below rope_start load the table's first row and ignore it: the load never waits for a branch
-    const int64_t at = (int64_t)(l > t.rope_start ? l - t.rope_start : 0) * D + d0;
-    const f32x4* c = reinterpret_cast<const f32x4*>(t.cos + at);
-    const f32x4* s = reinterpret_cast<const f32x4*>(t.sin + at);
-    const f32x4 c0 = c[0], c1 = c[1], s0 = s[0], s1 = s[1];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { tab.c[e] = c0[e]; tab.c[4 + e] = c1[e]; tab.s[e] = s0[e]; tab.s[4 + e] = s1[e]; }
-  } else {
-    const int64_t at = (int64_t)l * D + d0;   // pair p of row l is scalars 2*(l*D/2 + p), +1
-    if (t.freqs_f64) {
-      typedef double f64x2 __attribute__((ext_vector_type(2)));
-      const f64x2* z = reinterpret_cast<const f64x2*>(reinterpret_cast<const double*>(t.freqs) + at);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) { const f64x2 v = z[p]; tab.zr[p] = v[0]; tab.zi[p] = v[1]; }
-    } else {
-      const f32x4* z = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(t.freqs) + at);
-      const f32x4 a = z[0], b = z[1];
-      tab.zr[0] = a[0]; tab.zi[0] = a[1]; tab.zr[1] = a[2]; tab.zi[1] = a[3];
-      tab.zr[2] = b[0]; tab.zi[2] = b[1]; tab.zr[3] = b[2]; tab.zi[3] = b[3];
-    }
-  }
-}
 
 // One rounded operation each, whatever -ffp-contract says (this HIP release declares no __fmul_rn /
 // __fadd_rn, and the device library's *_rte entry points still fuse under -ffp-contract=fast): the
@@ -134,24 +77,6 @@ __device__ __forceinline__ void rope_complex(float (&f)[8], const RopeTab& tab) 
     f[2 * p] = round_to<T>(static_cast<float>(add_rn(mul_rn(a, tab.zr[p]), -mul_rn(b, tab.zi[p]))));
     f[2 * p + 1] = round_to<T>(static_cast<float>(add_rn(mul_rn(a, tab.zi[p]), mul_rn(b, tab.zr[p]))));
   }
-}
-
-// sum over the `lanes` (8, 16 or 64) neighbouring lanes that hold one head / one wave; every lane
-// of the wave takes part
-__device__ __forceinline__ float group_sum(float v, int lanes) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  if (lanes > 8) v += __shfl_xor(v, 8);
-  if (lanes > 16) {
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-  }
-  return v;
-}
-
-__device__ __forceinline__ float sum8(const float (&f)[8]) {
-  return ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
 }
 
 constexpr int kRedFloats = 2 * 2 * kMaxWaves;   // [row parity][tensor][wave]: the RMS partial sums
@@ -200,7 +125,7 @@ __global__ void __launch_bounds__(1024) qk_prologue_kernel(const QkTask task) {
         if (t < task.nt)
           raw[t] = __builtin_nontemporal_load(   // read once: leave the caches to the table and the output
               reinterpret_cast<const u32x4*>(task.t[t].x + (b * task.t[t].xs[0] + l * task.t[t].xs[1] + c0) * 2));
-      if (ROPE != VB_QK_ROPE_NONE) load_tab<ROPE>(task, l, D, d0, tab);
+      if (ROPE != VB_QK_ROPE_NONE) load_tab<ROPE>(task.rope, l, D, d0, tab);
     }
     float f[2][8];
 #pragma unroll
@@ -250,7 +175,7 @@ __global__ void __launch_bounds__(1024) qk_prologue_kernel(const QkTask task) {
         for (int e = 0; e < 8; ++e) x[e] = round_to<T>(wv[e] * (rstd * x[e]));
       }
       if (active) {
-        if (ROPE != VB_QK_ROPE_NONE && A.rope_on && l >= task.rope_start) {
+        if (ROPE != VB_QK_ROPE_NONE && A.rope_on && l >= task.rope.rope_start) {
           if (ROPE == VB_QK_ROPE_REAL) rope_real<T>(x, tab);
           else rope_complex<T>(x, tab);
         }
@@ -344,8 +269,7 @@ int launch(const vb_qk_prologue_args* const* a, const QkTensor* t, int n, hipStr
     if (t[i].norm_on) norm = a[i]->norm;
     if (t[i].rope_on && rope == VB_QK_ROPE_NONE) {
       rope = a[i]->rope;
-      task.rope_start = a[i]->rope_start;
-      task.cos = a[i]->cos; task.sin = a[i]->sin; task.freqs = a[i]->freqs; task.freqs_f64 = a[i]->freqs_f64;
+      task.rope = RopeSrc{a[i]->rope_start, a[i]->cos, a[i]->sin, a[i]->freqs, a[i]->freqs_f64};
     }
   }
   task.B = a[0]->B; task.L = a[0]->L; task.H = a[0]->H; task.D = a[0]->D;

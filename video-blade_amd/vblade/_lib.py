@@ -163,6 +163,27 @@ class QkPrologueArgs(ctypes.Structure):
     ]
 
 
+class QkPrologueBwdArgs(ctypes.Structure):
+    """vb_qk_prologue_bwd_args (include/vblade.h)."""
+    _fields_ = [
+        ("x", _vp), ("x_stride", ctypes.c_int64 * 2),
+        ("g", _vp), ("g_stride", _i64x3),
+        ("dx", _vp), ("dx_stride", ctypes.c_int64 * 2),
+        ("dweight", _vp), ("dbias", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_uint64),
+        ("B", ctypes.c_int), ("L", ctypes.c_int), ("H", ctypes.c_int), ("D", ctypes.c_int),
+        ("dtype", ctypes.c_int),
+        ("norm", ctypes.c_int),
+        ("weight", _vp), ("bias", _vp),
+        ("affine_f32", ctypes.c_int), ("eps", ctypes.c_float),
+        ("rope", ctypes.c_int), ("rope_start", ctypes.c_int),
+        ("cos", _vp), ("sin", _vp),
+        ("freqs", _vp), ("freqs_f64", ctypes.c_int),
+        ("grid_limit", ctypes.c_int),
+    ]
+
+
+VB_QK_BWD_MAX_GRID = 1024
 VB_QK_NORM_NONE, VB_QK_NORM_LAYER_HEAD, VB_QK_NORM_RMS_ROW = 0, 1, 2
 VB_QK_ROPE_NONE, VB_QK_ROPE_REAL, VB_QK_ROPE_COMPLEX = 0, 1, 2
 
@@ -221,6 +242,9 @@ SIGNATURES = {
         _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_float, ctypes.c_int, _vp, _vp, _vp]),
     "vb_qk_prologue": (ctypes.c_int, [ctypes.POINTER(QkPrologueArgs), ctypes.POINTER(QkPrologueArgs), _vp]),
+    "vb_qk_prologue_bwd_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(QkPrologueBwdArgs),
+                                                            ctypes.POINTER(QkPrologueBwdArgs)]),
+    "vb_qk_prologue_bwd": (ctypes.c_int, [ctypes.POINTER(QkPrologueBwdArgs), ctypes.POINTER(QkPrologueBwdArgs), _vp]),
 }
 
 _lib = None

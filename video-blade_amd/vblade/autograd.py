@@ -116,3 +116,51 @@ class _AdaptiveSplitFn(torch.autograd.Function):
 def adaptive_split_attention(q, k, v, mask, rows, gap, heavy_rows=2):
     """heavy_rows: forced-dense tail rows dispatched first (CogVideoX 2, Wan 0); scheduling only."""
     return _AdaptiveSplitFn.apply(q, k, v, mask, rows, gap, heavy_rows)
+
+
+class _QkPrologueFn(torch.autograd.Function):
+    """ops.qk_prologue out of place forward, ops.qk_prologue_bwd backward. Nothing but the inputs is
+    saved: the backward recomputes the norm's statistics."""
+
+    @staticmethod
+    def forward(ctx, q_proj, k_proj, q_weight, q_bias, k_weight, k_bias, kw):
+        ctx.set_materialize_grads(False)   # a None output gradient leaves that tensor out of the launch
+        ctx.kw = kw
+        ctx.save_for_backward(q_proj, k_proj, q_weight, q_bias, k_weight, k_bias)
+        return ops.qk_prologue(q_proj, k_proj, q_weight=q_weight, q_bias=q_bias, k_weight=k_weight,
+                               k_bias=k_bias, **kw)
+
+    @staticmethod
+    def backward(ctx, gq, gk=None):
+        q_proj, k_proj, q_weight, q_bias, k_weight, k_bias = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        use_q = gq is not None and (need[0] or need[2] or need[3])
+        use_k = gk is not None and (need[1] or need[4] or need[5])
+        if not (use_q or use_k):
+            return (None,) * 7
+        dq, dk, dqw, dqb, dkw, dkb = ops.qk_prologue_bwd(
+            q_proj if use_q else None, k_proj if use_k else None, gq=gq if use_q else None,
+            gk=gk if use_k else None, q_weight=q_weight, q_bias=q_bias, k_weight=k_weight, k_bias=k_bias,
+            need_wgrad=(use_q and need[2], use_q and need[3], use_k and need[4], use_k and need[5]), **ctx.kw)
+
+        def like(grad, param):   # the op sums in fp32; the gradient has the parameter's dtype and shape
+            return None if grad is None else grad.to(param.dtype).view(param.shape)
+
+        return (dq if need[0] else None, dk if need[1] else None, like(dqw, q_weight), like(dqb, q_bias),
+                like(dkw, k_weight), like(dkb, k_bias), None)
+
+
+def qk_prologue(q_proj, k_proj=None, *, heads, norm="none", q_weight=None, q_bias=None, q_eps=1e-5,
+                k_weight=None, k_bias=None, k_eps=None, rope="none", rope_start=0, cos=None, sin=None,
+                freqs=None):
+    """``ops.qk_prologue`` (out of place; there is no ``inplace`` here: the backward reads the
+    forward's input) differentiable in q_proj, k_proj and the norms' weights and biases, through
+    ``ops.qk_prologue_bwd``. Returns the same [B,heads,L,D] view(s). The RoPE tables are constants:
+    one that requires grad is refused. Parameter gradients are computed only where autograd asks
+    for them and come back in the parameter's dtype."""
+    for name, t in (("cos", cos), ("sin", sin), ("freqs", freqs)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"autograd.qk_prologue: {name} requires grad, but the RoPE tables get no gradient")
+    kw = dict(heads=heads, norm=norm, q_eps=q_eps, k_eps=k_eps, rope=rope, rope_start=rope_start,
+              cos=cos, sin=sin, freqs=freqs)
+    return _QkPrologueFn.apply(q_proj, k_proj, q_weight, q_bias, k_weight, k_bias, kw)

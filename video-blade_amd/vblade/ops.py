@@ -789,21 +789,9 @@ def _qk_table(name, t, shape, dev):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def qk_prologue(q_proj: torch.Tensor, k_proj: Optional[torch.Tensor] = None, *, heads: int,
-                norm="none", q_weight=None, q_bias=None, q_eps: float = 1e-5,
-                k_weight=None, k_bias=None, k_eps: Optional[float] = None,
-                rope="none", rope_start: int = 0, cos=None, sin=None, freqs=None,
-                inplace: bool = False):
-    """vb_qk_prologue: the attention processors' q/k norm and RoPE in one pass over q and k.
-
-    q_proj / k_proj: the projections' outputs, [B,L,heads*D] or [B,L,heads,D] (rows contiguous).
-    ``norm``: "none", "layer" (LayerNorm over each head's D values; weight/bias of D values) or "rms"
-    (RMSNorm over the heads*D row; weight of heads*D values); ``rope``: "none", "real" (cos/sin fp32
-    [L-rope_start, D] on the rows from ``rope_start``) or "complex" (``freqs``: a complex64/128
-    tensor of L*D/2 values, every row). A (q, k) pair gives each tensor its own mode, e.g.
-    ``rope=("real", "none")`` for cross attention. Weights are the storage dtype or fp32.
-    ``inplace`` overwrites the projections. Returns the [B,heads,L,D] view(s) the attention kernels
-    take — no transpose copy — as q or (q, k). Rounding points: include/vblade.h."""
+def _qk_modes(q_proj, k_proj, heads, norm, rope, rope_start, cos, sin, freqs):
+    """The checks qk_prologue and qk_prologue_bwd share: the per-tensor modes, the shape, and the RoPE
+    tables made ready for the launch. Returns (norms, ropes, dev, B, L, W, D, table)."""
     norms, ropes = _pair(norm), _pair(rope)
     for m in norms:
         if m not in QK_NORMS:
@@ -837,6 +825,26 @@ def qk_prologue(q_proj: torch.Tensor, k_proj: Optional[torch.Tensor] = None, *, 
         if freqs.numel() != L * (D // 2) or freqs.shape[-1] != D // 2:
             raise ValueError(f"qk_prologue: freqs must hold [{L}, {D // 2}] values, got {tuple(freqs.shape)}")
         table["freqs"] = _qk_table("freqs", torch.view_as_real(freqs.reshape(L, D // 2)), (L, D // 2, 2), dev)
+
+    return norms, ropes, dev, B, L, W, D, table
+
+
+def qk_prologue(q_proj: torch.Tensor, k_proj: Optional[torch.Tensor] = None, *, heads: int,
+                norm="none", q_weight=None, q_bias=None, q_eps: float = 1e-5,
+                k_weight=None, k_bias=None, k_eps: Optional[float] = None,
+                rope="none", rope_start: int = 0, cos=None, sin=None, freqs=None,
+                inplace: bool = False):
+    """vb_qk_prologue: the attention processors' q/k norm and RoPE in one pass over q and k.
+
+    q_proj / k_proj: the projections' outputs, [B,L,heads*D] or [B,L,heads,D] (rows contiguous).
+    ``norm``: "none", "layer" (LayerNorm over each head's D values; weight/bias of D values) or "rms"
+    (RMSNorm over the heads*D row; weight of heads*D values); ``rope``: "none", "real" (cos/sin fp32
+    [L-rope_start, D] on the rows from ``rope_start``) or "complex" (``freqs``: a complex64/128
+    tensor of L*D/2 values, every row). A (q, k) pair gives each tensor its own mode, e.g.
+    ``rope=("real", "none")`` for cross attention. Weights are the storage dtype or fp32.
+    ``inplace`` overwrites the projections. Returns the [B,heads,L,D] view(s) the attention kernels
+    take — no transpose copy — as q or (q, k). Rounding points: include/vblade.h."""
+    norms, ropes, dev, B, L, W, D, table = _qk_modes(q_proj, k_proj, heads, norm, rope, rope_start, cos, sin, freqs)
 
     keep = []   # tensors the launch reads stay alive until it is enqueued
 
@@ -891,6 +899,105 @@ def qk_prologue(q_proj: torch.Tensor, k_proj: Optional[torch.Tensor] = None, *, 
     if k_proj is None:
         return q_view
     return q_view, k_out.view(B, L, heads, D).transpose(1, 2)
+
+
+def qk_prologue_bwd(q_proj: Optional[torch.Tensor] = None, k_proj: Optional[torch.Tensor] = None, *,
+                    gq: Optional[torch.Tensor] = None, gk: Optional[torch.Tensor] = None, heads: int,
+                    norm="none", q_weight=None, q_bias=None, q_eps: float = 1e-5,
+                    k_weight=None, k_bias=None, k_eps: Optional[float] = None,
+                    rope="none", rope_start: int = 0, cos=None, sin=None, freqs=None,
+                    need_wgrad=(False, False, False, False), grid_limit: int = 0):
+    """vb_qk_prologue_bwd: the backward of ``qk_prologue`` in one pass over q and k.
+
+    The forward's inputs and keywords (without ``inplace``), plus ``gq`` / ``gk``: the gradients
+    w.r.t. the [B,heads,L,D] views the forward returned, in any memory whose strides are multiples
+    of 8 ([B,H,L,D]-contiguous or the transposed view of [B,L,H,D] memory; anything else is copied).
+    A tensor whose gradient is None is left out of the launch. ``need_wgrad`` = (q_w, q_b, k_w, k_b)
+    asks for the norm parameters' gradients (fp32, summed in an order fixed by the shape and
+    ``grid_limit``; 0 = the library's own grid). Returns (dq_proj, dk_proj, dq_w, dq_b, dk_w, dk_b)
+    with None where not requested; dq_proj / dk_proj have the projections' shape and dtype."""
+    if gq is None and gk is None:
+        raise ValueError("qk_prologue_bwd: gq and gk are both None")
+    if (gq is not None and q_proj is None) or (gk is not None and k_proj is None):
+        raise ValueError("qk_prologue_bwd: a gradient needs the forward's input of its tensor")
+    first = q_proj if q_proj is not None else k_proj
+    norms, ropes, dev, B, L, W, D, table = _qk_modes(first, k_proj if q_proj is not None else None, heads, norm, rope,
+                                                     rope_start, cos, sin, freqs)
+    keep = []   # tensors the launch reads stay alive until it is enqueued
+    outs = []
+
+    def fill(x, g, mode, rmode, w, b, eps, want_w, want_b):
+        if tuple(g.shape) != (B, heads, L, D) or g.dtype != x.dtype:
+            raise ValueError(f"qk_prologue_bwd: a gradient must be [{B},{heads},{L},{D}] {x.dtype}, got "
+                             f"{tuple(g.shape)} {g.dtype}")
+        _check_dev("qk_prologue_bwd: gradient", g, dev)
+        x3 = x.detach().reshape(B, L, W) if x.dim() == 4 else x.detach()
+        if not (x3.stride(2) == 1 and (B == 1 or x3.stride(0) % 8 == 0) and x3.stride(1) % 8 == 0
+                and x3.stride(1) >= W and x3.data_ptr() % 16 == 0):
+            x3 = x3.contiguous()
+        g = g.detach()
+        if not (g.stride(3) == 1 and (B == 1 or g.stride(0) % 8 == 0) and g.stride(1) % 8 == 0 and g.stride(2) % 8 == 0
+                and (heads == 1 or g.stride(1) >= D) and g.data_ptr() % 16 == 0):
+            g = g.contiguous()
+        dx = torch.empty(B, L, W, device=dev, dtype=x.dtype)
+        a = _lib.QkPrologueBwdArgs()
+        a.x, a.g, a.dx = x3.data_ptr(), g.data_ptr(), dx.data_ptr()
+        a.x_stride = (ctypes.c_int64 * 2)(x3.stride(0) if B > 1 else 0, x3.stride(1))
+        a.g_stride = (ctypes.c_int64 * 3)(g.stride(0) if B > 1 else 0, g.stride(2), g.stride(1) if heads > 1 else D)
+        a.dx_stride = (ctypes.c_int64 * 2)(dx.stride(0) if B > 1 else 0, dx.stride(1))
+        a.B, a.L, a.H, a.D = B, L, heads, D
+        a.dtype = _dtype_code(x)
+        a.norm = QK_NORMS[mode]
+        if mode == "none" and (w is not None or b is not None):
+            raise ValueError("qk_prologue_bwd: weight/bias given without a norm")
+        if mode == "rms" and b is not None:
+            raise ValueError("qk_prologue_bwd: the RMSNorm takes no bias")
+        if (want_w and w is None) or (want_b and b is None):
+            raise ValueError("qk_prologue_bwd: need_wgrad asks for the gradient of a parameter that was not given")
+        n = D if mode == "layer" else W
+        w, b = _qk_affine("weight", w, n, x, dev), _qk_affine("bias", b, n, x, dev)
+        if w is not None and b is not None and w.dtype != b.dtype:
+            raise TypeError("qk_prologue_bwd: weight and bias must share a dtype")
+        a.weight, a.bias = _ptr(w), _ptr(b)
+        a.affine_f32 = int(any(t is not None and t.dtype == torch.float32 for t in (w, b)))
+        a.eps = float(eps)
+        a.rope = QK_ROPES[rmode]
+        if rmode == "real":
+            a.rope_start = int(rope_start)
+            a.cos, a.sin = table["cos"].data_ptr(), table["sin"].data_ptr()
+        elif rmode == "complex":
+            a.freqs = table["freqs"].data_ptr()
+            a.freqs_f64 = int(table["freqs"].dtype == torch.float64)
+        a.grid_limit = int(grid_limit)
+        dw = torch.empty(n, device=dev, dtype=torch.float32) if want_w else None
+        db = torch.empty(n, device=dev, dtype=torch.float32) if want_b else None
+        a.dweight, a.dbias = _ptr(dw), _ptr(db)
+        keep.extend((x3, g, w, b))
+        outs.append((dx.view(x.shape), dw, db))
+        return a
+
+    want = [bool(v) for v in need_wgrad]
+    qa = ka = None
+    if gq is not None:
+        qa = fill(q_proj, gq, norms[0], ropes[0], q_weight, q_bias, q_eps, want[0], want[1])
+    else:
+        outs.append((None, None, None))
+    if gk is not None:
+        ka = fill(k_proj, gk, norms[1], ropes[1], k_weight, k_bias, q_eps if k_eps is None else k_eps, want[2], want[3])
+    else:
+        outs.append((None, None, None))
+    lib = _lib.load()
+    refs = [ctypes.byref(a) if a is not None else None for a in (qa, ka)]
+    nbytes = lib.vb_qk_prologue_bwd_workspace_size(*refs)
+    if nbytes:
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        head = qa if qa is not None else ka     # the first tensor of the call names the workspace
+        head.workspace, head.workspace_bytes = ws.data_ptr(), nbytes
+        keep.append(ws)
+    check(lib.vb_qk_prologue_bwd(*refs, _stream(dev)), "vb_qk_prologue_bwd")
+    del keep
+    (dq, dqw, dqb), (dk, dkw, dkb) = outs
+    return dq, dk, dqw, dqb, dkw, dkb
 
 
 # ----------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 
 Mirrors cogvideox/train/modify_cogvideo.py:11-91 and wanx/train/modify_wan.py:75-168. The
 processors are the callers of the hot path (the QKV projections stay in PyTorch; so do the norms
-and RoPE unless ``fused_qk=True`` hands them to the library's one-pass prologue, ops.qk_prologue);
+and RoPE unless ``fused_qk=True`` hands them to the library's one-pass prologue, ops.qk_prologue,
+and with ``fused_qk_backward=True`` also under autograd, through autograd.qk_prologue);
 ``attn.inner_attention(q, k, v)`` is the vblade module. diffusers is imported lazily and only
 for its RoPE helper; nothing here needs it at import time.
 """
@@ -12,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import autograd, ops
 from .attention import AdaptiveBlockSparseAttn
 
 
@@ -34,16 +35,20 @@ def _apply_rotary_emb_real(x: torch.Tensor, freqs_cis) -> torch.Tensor:
 # fused_qk: which calls the one-pass prologue (ops.qk_prologue) may take. Anything it cannot
 # identify exactly keeps the eager chain, silently and completely.
 # ---------------------------------------------------------------------------------------------
-def _prologue_inputs_ok(query, key, value, heads, head_dim, *params) -> bool:
+def _records_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def _prologue_inputs_ok(query, key, value, heads, head_dim, *params, backward: bool = False) -> bool:
     """HIP tensors of one 16-bit dtype and one shape, a head size the kernel has, and no autograd
-    recording (the prologue has no backward)."""
+    recording unless ``backward`` (fused_qk_backward) lets the call take autograd.qk_prologue."""
     if not (query.is_cuda and key.is_cuda and query.dtype in (torch.bfloat16, torch.float16)):
         return False
     if key.dtype != query.dtype or value.dtype != query.dtype or key.shape != query.shape:
         return False
     if head_dim not in (64, 128) or heads * head_dim > 8192:
         return False
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (query, key, *params)):
+    if not backward and _records_grad(query, key, *params):
         return False
     return True
 
@@ -84,21 +89,25 @@ class CogVideoXBlockSparseAttnProcessor:
     """SageAttnCogVideoXAttnProcessor (modify_cogvideo.py:11-76): joint text+video self-attention
     whose inner attention is ``attn.inner_attention``. Text tokens come FIRST in the sequence.
     ``fused_qk``: norm_q/norm_k and RoPE in one library pass where the call allows it (see
-    ``_fused_qk``); ``last_path`` tells which chain the last call took, "fused" or "eager"."""
+    ``_fused_qk``); ``last_path`` tells which chain the last call took, "fused" or "eager".
+    ``fused_qk_backward`` (with ``fused_qk``): a call that records autograd takes the fused pass too,
+    through autograd.qk_prologue, instead of keeping the eager chain."""
 
-    def __init__(self, idx: int = 0, fused_qk: bool = False):
+    def __init__(self, idx: int = 0, fused_qk: bool = False, fused_qk_backward: bool = False):
         self.idx = idx
         self.fused_qk = fused_qk
+        self.fused_qk_backward = fused_qk_backward
         self.last_path = None
 
     def _fused_qk(self, attn, query, key, value, head_dim, text_seq_length, image_rotary_emb):
         """(q, k) [B,H,L,D] from the [B,L,H*D] projections through ops.qk_prologue, or None when this
-        call keeps the eager chain: CPU or fp32 tensors, autograd recording, a norm that is not
-        exactly nn.LayerNorm((head_dim,)), or rotary tables that are not a (cos, sin) pair of fp32
-        [video rows, head_dim]."""
+        call keeps the eager chain: CPU or fp32 tensors, autograd recording without
+        ``fused_qk_backward``, a norm that is not exactly nn.LayerNorm((head_dim,)), or rotary tables
+        that are not a (cos, sin) pair of fp32 [video rows, head_dim]."""
         norm_q, norm_k = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
-        if not _prologue_inputs_ok(query, key, value, attn.heads, head_dim,
-                                   *_norm_params(norm_q), *_norm_params(norm_k)):
+        params = (*_norm_params(norm_q), *_norm_params(norm_k))
+        if not _prologue_inputs_ok(query, key, value, attn.heads, head_dim, *params,
+                                   backward=self.fused_qk_backward):
             return None
         nq = _layer_norm_spec(norm_q, head_dim, query.dtype)
         nk = _layer_norm_spec(norm_k, head_dim, query.dtype)
@@ -115,10 +124,10 @@ class CogVideoXBlockSparseAttnProcessor:
                 return None
             rope = "real"
         k_rope = "none" if getattr(attn, "is_cross_attention", False) else rope
-        return ops.qk_prologue(query, key, heads=attn.heads, norm=(nq[0], nk[0]),
-                               q_weight=nq[1], q_bias=nq[2], q_eps=nq[3],
-                               k_weight=nk[1], k_bias=nk[2], k_eps=nk[3],
-                               rope=(rope, k_rope), rope_start=text_seq_length, cos=cos, sin=sin)
+        op = autograd.qk_prologue if _records_grad(query, key, *params) else ops.qk_prologue
+        return op(query, key, heads=attn.heads, norm=(nq[0], nk[0]),
+                  q_weight=nq[1], q_bias=nq[2], q_eps=nq[3], k_weight=nk[1], k_bias=nk[2], k_eps=nk[3],
+                  rope=(rope, k_rope), rope_start=text_seq_length, cos=cos, sin=sin)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states, attention_mask=None,
                  image_rotary_emb=None):
@@ -161,14 +170,17 @@ class CogVideoXBlockSparseAttnProcessor:
 def set_block_sparse_attn_cogvideox(model, verbose: bool = False, **attn_kwargs):
     """modify_cogvideo.py:79-91: ONE shared inner-attention module on every transformer block's
     attn1, processor swapped, the original kept as ``origin_processor``. Returns the module.
-    ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE."""
+    ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE;
+    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training)."""
     fused_qk = bool(attn_kwargs.pop("fused_qk", False))
+    fused_qk_backward = bool(attn_kwargs.pop("fused_qk_backward", False))
     inner_attn = AdaptiveBlockSparseAttn("cog", **attn_kwargs)
     for idx, block in enumerate(model.transformer_blocks):
         block.attn1.verbose = verbose
         block.attn1.inner_attention = inner_attn
         origin = block.attn1.get_processor() if hasattr(block.attn1, "get_processor") else None
-        block.attn1.set_processor(CogVideoXBlockSparseAttnProcessor(idx, fused_qk=fused_qk))
+        block.attn1.set_processor(CogVideoXBlockSparseAttnProcessor(
+            idx, fused_qk=fused_qk, fused_qk_backward=fused_qk_backward))
         if not hasattr(block.attn1, "origin_processor"):
             block.attn1.origin_processor = origin
     return inner_attn
@@ -177,17 +189,18 @@ def set_block_sparse_attn_cogvideox(model, verbose: bool = False, **attn_kwargs)
 class WanBlockSparseAttnProcessor:
     """WanAttnProcessor2_0 (modify_wan.py:75-148): video self-attention (attn1) with the
     complex-valued RoPE in float64; the I2V image branch also goes through inner_attention.
-    ``fused_qk`` / ``last_path``: as CogVideoXBlockSparseAttnProcessor."""
+    ``fused_qk`` / ``fused_qk_backward`` / ``last_path``: as CogVideoXBlockSparseAttnProcessor."""
 
-    def __init__(self, fused_qk: bool = False):
+    def __init__(self, fused_qk: bool = False, fused_qk_backward: bool = False):
         self.fused_qk = fused_qk
+        self.fused_qk_backward = fused_qk_backward
         self.last_path = None
 
     def _fused_qk(self, attn, query, key, value, rotary_emb):
         """(q, k) [B,H,L,D] through ops.qk_prologue, or None when this call keeps the eager chain: the
-        I2V image branch, k of another length than q, CPU or fp32 tensors, autograd recording, a norm
-        that is not exactly nn.RMSNorm((heads*head_dim,)), or a rotary table that is not a complex
-        [1,1,L,head_dim/2] tensor."""
+        I2V image branch, k of another length than q, CPU or fp32 tensors, autograd recording without
+        ``fused_qk_backward``, a norm that is not exactly nn.RMSNorm((heads*head_dim,)), or a rotary
+        table that is not a complex [1,1,L,head_dim/2] tensor."""
         if getattr(attn, "add_k_proj", None) is not None or query.dim() != 3:
             return None
         width = query.shape[-1]
@@ -195,8 +208,9 @@ class WanBlockSparseAttnProcessor:
             return None
         head_dim = width // attn.heads
         norm_q, norm_k = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
-        if not _prologue_inputs_ok(query, key, value, attn.heads, head_dim,
-                                   *_norm_params(norm_q), *_norm_params(norm_k)):
+        params = (*_norm_params(norm_q), *_norm_params(norm_k))
+        if not _prologue_inputs_ok(query, key, value, attn.heads, head_dim, *params,
+                                   backward=self.fused_qk_backward):
             return None
         nq = _rms_norm_spec(norm_q, width, query.dtype)
         nk = _rms_norm_spec(norm_k, width, query.dtype)
@@ -209,9 +223,9 @@ class WanBlockSparseAttnProcessor:
                     and not rotary_emb.requires_grad):
                 return None
             rope = "complex"
-        return ops.qk_prologue(query, key, heads=attn.heads, norm=(nq[0], nk[0]),
-                               q_weight=nq[1], q_eps=nq[3], k_weight=nk[1], k_eps=nk[3],
-                               rope=rope, freqs=rotary_emb)
+        op = autograd.qk_prologue if _records_grad(query, key, *params) else ops.qk_prologue
+        return op(query, key, heads=attn.heads, norm=(nq[0], nk[0]),
+                  q_weight=nq[1], q_eps=nq[3], k_weight=nk[1], k_eps=nk[3], rope=rope, freqs=rotary_emb)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None,
                  rotary_emb: Optional[torch.Tensor] = None):
@@ -262,14 +276,17 @@ class WanBlockSparseAttnProcessor:
 def set_adaptive_block_sparse_attn_wanx(model, verbose: bool = False, **attn_kwargs):
     """modify_wan.py:150-168: patch attn1 (self-attention) of every block; attn2 (cross-attention
     to the T5 tokens) keeps stock SDPA. Returns the shared module.
-    ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE."""
+    ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE;
+    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training)."""
     fused_qk = bool(attn_kwargs.pop("fused_qk", False))
+    fused_qk_backward = bool(attn_kwargs.pop("fused_qk_backward", False))
     inner_attn = AdaptiveBlockSparseAttn("wan", **attn_kwargs)
     for block in model.blocks:
         block.attn1.verbose = verbose
         block.attn1.inner_attention = inner_attn
         origin = block.attn1.get_processor() if hasattr(block.attn1, "get_processor") else None
-        block.attn1.set_processor(WanBlockSparseAttnProcessor(fused_qk=fused_qk))
+        block.attn1.set_processor(WanBlockSparseAttnProcessor(fused_qk=fused_qk,
+                                                               fused_qk_backward=fused_qk_backward))
         if not hasattr(block.attn1, "origin_processor"):
             block.attn1.origin_processor = origin
     return inner_attn
