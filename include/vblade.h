@@ -570,6 +570,62 @@ uint64_t vb_qk_prologue_bwd_workspace_size(const vb_qk_prologue_bwd_args* q, con
  * name two different norms or two different RoPE tables. */
 int vb_qk_prologue_bwd(const vb_qk_prologue_bwd_args* q, const vb_qk_prologue_bwd_args* k, void* stream);
 
+/* ==========================================================================================
+ * Head-adaptive retain budgets: the reference's judge_sparsity estimator (cogvideox/train/
+ * special_attentions_local/TrainRelated/blocksparseattn.py:147-160) and the budget rule of its
+ * commented-out call sites (cogvideo_blocksparseattn.py:344-348; wanx_blocksparseattn.py:328-330),
+ * on the device. Additive to ABI 4.
+ *
+ * vb_judge_sparsity: for every (b,h) and every sampled row r < S, over the n = ceil(L / key_stride)
+ * keys j*key_stride (j = 0 .. n-1):
+ *   s_j    = scale * <q[b,h,rows[r],:], k[b,h,j*key_stride,:]>, MFMA with fp32 accumulation
+ *   p      = softmax(s) over the n keys, max-subtracted, fp32 (exp2 on scale*log2(e)-scaled scores)
+ *   mass_r = the sum of the top_n largest p_j: with t the top_n-th largest value, found by a radix
+ *            selection over the fp32 bit patterns (no sort), sum(p > t) + (top_n - #(p > t)) * t, so
+ *            ties at the boundary count the same whichever of them is taken
+ *   sparsity[b,h] = the fp32 mean of mass_r over r, summed serially in r order
+ * which is the reference's sort-descending / mean-by-rank / sum of the first top_n ranks: the mean
+ * over rows of each row's top-n mass. The Python side passes top_n = int(n * 0.2).
+ * q, k: [B,H,L,D] strided (unit d-stride, strides multiples of 8 elements, 16-byte aligned bases),
+ * read in place; D = 64 or 128, L <= 131072, every (b,h) slice < 2 GiB (else VB_ERR_UNSUPPORTED).
+ * rows: DEVICE int32 [S], caller row numbers shared by all (b,h), S in [1, 64]. They cannot be
+ * checked on the host without a synchronisation: the kernel clamps each to [0, L-1] before it is
+ * used as an address. top_n in [1, n]. Null pointers, S, top_n or key_stride out of range and a
+ * short workspace are VB_ERR_INVALID before any launch.
+ * sparsity: fp32 [B,H]; row_mass (nullable): fp32 [B,H,S], mass_r.
+ * workspace: device, 16-byte aligned, >= vb_judge_sparsity_workspace_size(args) bytes (host
+ * arithmetic: B*H*S rows of n fp32 scores, each padded to a multiple of four, staged between the
+ * two launches of the call, plus B*H*S row masses and B*H counters).
+ * Deterministic: no floating-point atomics, every sum in an order fixed by the shape; two calls
+ * give the same bits. Two launches on `stream`.
+ * ========================================================================================== */
+typedef struct vb_judge_args {
+  const void* q; const void* k;
+  int64_t q_stride[3]; int64_t k_stride[3];
+  const int32_t* rows;      /* device [S] */
+  int B, H, L, D, S;
+  int key_stride;           /* >= 1; the reference's k[:, :, ::3] is 3 */
+  int top_n;
+  float scale;              /* <= 0 -> D^-1/2 */
+  int dtype;
+  float* sparsity;          /* [B,H] */
+  float* row_mass;          /* [B,H,S] or NULL */
+  void* workspace; uint64_t workspace_bytes;
+} vb_judge_args;
+uint64_t vb_judge_sparsity_workspace_size(const vb_judge_args* args);
+int vb_judge_sparsity(const vb_judge_args* args, void* stream);
+
+/* The budget rule on the device: sparsity fp32 [B,H] -> max_keep int32 [B,H] (the array
+ * vb_mask_rule.max_keep takes) and, when non-NULL, ratio fp32 [B,H]. In float64:
+ *   m     = (sum of all B*H values) / (B*H)       (batch and heads together, the reference's .mean())
+ *   ratio = min(max(base * (sparsity[b,h] / m), lo), hi)
+ *   count = max(1, int(float(nb) * float(ratio)))  arith 0 (cog: an fp32 product)
+ *           max(1, int(nb * ratio))                arith 1 (wan: float64)
+ * the two arithmetics of the per-head retain counts elsewhere in this library's Python layer. One
+ * launch on `stream`. base > 0, finite lo <= hi, nb >= 1, arith 0 or 1, else VB_ERR_INVALID. */
+int vb_head_budget(const float* sparsity, int B, int H, int nb, double base, double lo, double hi,
+                   int arith, int32_t* max_keep, float* ratio, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

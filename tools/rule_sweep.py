@@ -7,11 +7,16 @@ second default module gives the A/A spread.
 Settings: the default energy rule (scalar bounds: vb_mask_predict), the same rule with its bounds as
 uniform per-head arrays (vb_mask_predict_rule: what the rule instantiation itself costs), top-k mode
 at init_k 0.05 / 0.1 / 0.2, and one per-head budget set (the odd heads at half the default
-max_retain_ratio). Per setting: the predictor's launches as the module issues them (pooled K/V pass
+max_retain_ratio), and the head-adaptive budget: `judge` (head_budget="judge": the estimator and
+the budget rule before the predictor, every call) and `judge/clamp(r,r)` with r the default
+max_retain_ratio, whose masks are those of `energy/uniform[H]`, so their difference in call time is
+the estimator's pure overhead (call_vs_uniform). bench.local_qkv's heads are statistically alike, so
+the estimator has nothing to find there: --head-temps LO HI scales q per head (linspace over the
+heads), which gives the heads different concentrations. Per setting: the predictor's launches as the module issues them (pooled K/V pass
 riding), the whole module call and its ratio to the default, the kept-block fraction, and the PSNR
 of the module output against dense SDPA on the same inputs.
 
-usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--out FILE.json]
+usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--out FILE.json]
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/rule_sweep.py --variant cog --one-call SETTING
        (four module calls of one setting and nothing else: a kernel trace then shows its launches
        per call, tools/kstats.py DIR)"""
@@ -64,12 +69,23 @@ def settings(variant, H):
     half = torch.full((H,), d["max_retain_ratio"])
     half[1::2] *= 0.5
     mods["energy/odd heads at half max"] = mk(max_retain_ratio=half)
+    mods["judge"] = mk(head_budget="judge")
+    r = d["max_retain_ratio"]
+    mods["judge/clamp(r,r)"] = mk(head_budget="judge", judge_clamp=(r, r))
     return mods
 
 
-def sweep(variant, rounds, dev):
-    H, D = (48, 64) if variant == "cog" else (12, 128)
+def inputs(variant, H, D, dev, temps):
     q, k, v = local_qkv(variant, H, D, 0, dev)
+    if temps is not None:
+        t = torch.linspace(temps[0], temps[1], H, device=dev).view(1, H, 1, 1)
+        q = (q.float() * t).to(q.dtype)
+    return q, k, v
+
+
+def sweep(variant, rounds, dev, temps=None):
+    H, D = (48, 64) if variant == "cog" else (12, 128)
+    q, k, v = inputs(variant, H, D, dev, temps)
     L = q.shape[2]
     mods = settings(variant, H)
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
@@ -94,6 +110,11 @@ def sweep(variant, rounds, dev):
             out = work[lab]["call_ms"]()
             torch.cuda.synchronize()
             res[lab] = {"kept_fraction": m.last_mask.float().mean().item(), "psnr_vs_dense_db": psnr(out, dense)}
+            if m.head_budget == "judge":
+                b = m.last_head_budget.flatten().tolist()
+                sp = m.last_head_sparsity.flatten().tolist()
+                res[lab].update(head_budget_min=min(b), head_budget_max=max(b), head_budget_mean=sum(b) / len(b),
+                                head_sparsity_min=min(sp), head_sparsity_max=max(sp))
             work[lab]["pred_fused_ms"]()
         times = {lab: {f: [] for f in work[lab]} for lab in mods}
         for _ in range(rounds):
@@ -105,8 +126,11 @@ def sweep(variant, rounds, dev):
             res[lab][f] = statistics.median(ts)
             res[lab][f + "_min"] = min(ts)
             res[lab][f.replace("_ms", "_vs_energy")] = res[lab][f] / statistics.median(times["energy"][f])
+            res[lab][f.replace("_ms", "_vs_uniform")] = res[lab][f] / statistics.median(times["energy/uniform[H]"][f])
+    same = torch.equal(mods["judge/clamp(r,r)"].last_mask, mods["energy/uniform[H]"].last_mask)
     return {"variant": variant, "B": 1, "H": H, "L": L, "D": D, "nb": (L + 127) // 128,
-            "inputs": "bench.local_qkv(seed 0)", "rounds": rounds, "calls_per_round": 5, "settings": res}
+            "inputs": "bench.local_qkv(seed 0)" + ("" if temps is None else f", q scaled per head {temps[0]}..{temps[1]}"),
+            "rounds": rounds, "calls_per_round": 5, "clamp_rr_mask_equals_uniform": same, "settings": res}
 
 
 def main():
@@ -115,13 +139,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--out", default=None)
     ap.add_argument("--one-call", default=None, metavar="SETTING")
+    ap.add_argument("--head-temps", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.one_call:
         variant = "cog" if a.variant == "both" else a.variant
         H, D = (48, 64) if variant == "cog" else (12, 128)
         m = settings(variant, H)[a.one_call]
-        q, k, v = local_qkv(variant, H, D, 0, dev)
+        q, k, v = inputs(variant, H, D, dev, a.head_temps)
         with torch.no_grad():
             for _ in range(4):
                 m(q, k, v)
@@ -130,14 +155,19 @@ def main():
         return
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
-        r = sweep(variant, a.rounds, dev)
+        r = sweep(variant, a.rounds, dev, a.head_temps)
         out["results"].append(r)
-        print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks)")
-        print("  setting                      | fused pred ms (x energy) | call ms (x energy) | kept   | PSNR dB")
+        print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks), inputs {r['inputs']}; "
+              f"judge/clamp(r,r) mask == energy/uniform[H] mask: {r['clamp_rr_mask_equals_uniform']}")
+        print("  setting                      | fused pred ms (x energy) | call ms (x energy, x uniform[H]) | kept   | PSNR dB")
         for lab, d in r["settings"].items():
+            extra = ""
+            if "head_budget_min" in d:
+                extra = (f" | budgets {d['head_budget_min']}..{d['head_budget_max']} (mean {d['head_budget_mean']:.2f}), "
+                         f"sparsity {d['head_sparsity_min']:.3f}..{d['head_sparsity_max']:.3f}")
             print(f"  {lab:<28} | {d['pred_fused_ms']:.4f} ({d['pred_fused_vs_energy']:.3f}) | "
-                  f"{d['call_ms']:.4f} ({d['call_vs_energy']:.3f}) | {d['kept_fraction']:.4f} | "
-                  f"{d['psnr_vs_dense_db']:.2f}", flush=True)
+                  f"{d['call_ms']:.4f} ({d['call_vs_energy']:.3f}, {d['call_vs_uniform']:.3f}) | {d['kept_fraction']:.4f} | "
+                  f"{d['psnr_vs_dense_db']:.2f}{extra}", flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

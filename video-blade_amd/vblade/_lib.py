@@ -183,6 +183,23 @@ class QkPrologueBwdArgs(ctypes.Structure):
     ]
 
 
+class JudgeArgs(ctypes.Structure):
+    """vb_judge_args (include/vblade.h)."""
+    _fields_ = [
+        ("q", _vp), ("k", _vp),
+        ("q_stride", _i64x3), ("k_stride", _i64x3),
+        ("rows", _vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("L", ctypes.c_int), ("D", ctypes.c_int),
+        ("S", ctypes.c_int),
+        ("key_stride", ctypes.c_int), ("top_n", ctypes.c_int),
+        ("scale", ctypes.c_float),
+        ("dtype", ctypes.c_int),
+        ("sparsity", _vp), ("row_mass", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
+VB_JUDGE_MAX_SAMPLES = 64
 VB_QK_BWD_MAX_GRID = 1024
 VB_QK_NORM_NONE, VB_QK_NORM_LAYER_HEAD, VB_QK_NORM_RMS_ROW = 0, 1, 2
 VB_QK_ROPE_NONE, VB_QK_ROPE_REAL, VB_QK_ROPE_COMPLEX = 0, 1, 2
@@ -245,6 +262,11 @@ SIGNATURES = {
     "vb_qk_prologue_bwd_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(QkPrologueBwdArgs),
                                                             ctypes.POINTER(QkPrologueBwdArgs)]),
     "vb_qk_prologue_bwd": (ctypes.c_int, [ctypes.POINTER(QkPrologueBwdArgs), ctypes.POINTER(QkPrologueBwdArgs), _vp]),
+    "vb_judge_sparsity_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(JudgeArgs)]),
+    "vb_judge_sparsity": (ctypes.c_int, [ctypes.POINTER(JudgeArgs), _vp]),
+    "vb_head_budget": (ctypes.c_int, [
+        _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+        ctypes.c_int, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -142,6 +142,16 @@ class AdaptiveBlockSparseAttn(nn.Module):
     once per (tensor, B, H, nb, device); a steady-state call launches nothing extra and never
     synchronises. Either option runs the mask rule in the predictor's own launch
     (vb_mask_predict_rule); without them the module makes the calls it always made.
+    head_budget: None (default) or "judge": every call estimates each head's concentration from its own
+    q and k (ops.judge_sparsity: ``judge_samples`` probe rows against every ``judge_key_stride``-th
+    key, the softmax mass of the top ``judge_top`` of the keys) and gives head (b,h) the budget
+    clamp(max_retain_ratio * sparsity / sparsity.mean(), *judge_clamp) (ops.head_budget; the
+    reference's commented-out lines, cogvideo_blocksparseattn.py:344-348) as its energy rule's
+    max_keep. max_retain_ratio must then be a float and mask_mode "energy". The probe rows are drawn
+    once, at construction, from a CPU generator seeded with ``judge_seed`` (distinct video rows; the
+    non-persistent buffer ``judge_rows``, which may be overwritten; ``forward(judge_rows=...)``
+    overrides it for one call), so a call consumes no random numbers. ``last_head_sparsity`` (fp32
+    [B,H]) and ``last_head_budget`` (int32 [B,H]) stay on the device.
     """
 
     def __init__(self, variant: str = "cog", *, combine: str = "fused", **overrides):
@@ -151,7 +161,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
         cfg = dict(VARIANT_DEFAULTS[variant])
         unknown = set(overrides) - set(cfg) - {"energy_threshold", "block", "num_keep", "overlap", "gather_kv",
                                                "mask_head_mode", "order", "order_window", "persistent",
-                                               "mask_mode", "init_k"}
+                                               "mask_mode", "init_k", "head_budget", "judge_samples",
+                                               "judge_key_stride", "judge_top", "judge_clamp", "judge_seed"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
@@ -172,6 +183,39 @@ class AdaptiveBlockSparseAttn(nn.Module):
         if self.mask_mode == "topk" and (self.init_k is None or not self.init_k > 0):
             raise ValueError("mask_mode='topk' needs init_k > 0 (a ratio below 1 or a block count)")
         self._per_head_cache = {}
+        self.head_budget = cfg.get("head_budget")
+        self.judge_samples = int(cfg.get("judge_samples", 30))
+        self.judge_key_stride = int(cfg.get("judge_key_stride", 3))
+        self.judge_top = float(cfg.get("judge_top", 0.2))
+        self.judge_clamp = tuple(float(c) for c in cfg.get("judge_clamp", (0.05, 0.9)))
+        self.judge_seed = int(cfg.get("judge_seed", 0))
+        self.last_head_sparsity: Optional[torch.Tensor] = None
+        self.last_head_budget: Optional[torch.Tensor] = None
+        if self.head_budget not in (None, "judge"):
+            raise ValueError(f"head_budget must be None or 'judge', got {self.head_budget!r}")
+        if self.head_budget == "judge":
+            if self.mask_mode != "energy":
+                raise ValueError("head_budget='judge' sets the energy rule's max_keep: mask_mode must be 'energy'")
+            if isinstance(self.max_retain_ratio, torch.Tensor):
+                raise ValueError("head_budget='judge' scales a float max_retain_ratio per head; a tensor "
+                                 "max_retain_ratio already is a per-head budget")
+            if not 1 <= self.judge_samples <= ops.JUDGE_MAX_SAMPLES:
+                raise ValueError(f"judge_samples must be in [1, {ops.JUDGE_MAX_SAMPLES}], got {self.judge_samples}")
+            if len(self.judge_clamp) != 2 or not self.judge_clamp[0] <= self.judge_clamp[1]:
+                raise ValueError(f"judge_clamp must be (lo, hi) with lo <= hi, got {self.judge_clamp}")
+            if self.judge_key_stride < 1 or not 0.0 < self.judge_top <= 1.0:
+                raise ValueError("judge_key_stride must be >= 1 and judge_top in (0, 1]")
+            video = int(cfg["width"]) * int(cfg["height"]) * int(cfg["depth"])
+            if self.judge_samples > video:
+                raise ValueError(f"judge_samples {self.judge_samples} exceeds the {video} video tokens")
+            # the probe: judge_samples distinct video rows, drawn ONCE from a CPU generator (the
+            # reference's randperm(width*height)[:sample_num] + text_length draws anew per call and from
+            # the first frame only; assign such rows to the buffer to get that). A fixed probe keeps
+            # the call free of RNG use, identical under checkpoint recompute, and capturable.
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(self.judge_seed)
+            probe = self.text_length + torch.randperm(video, generator=gen)[:self.judge_samples]
+            self.register_buffer("judge_rows", probe.to(torch.int32), persistent=False)
         self.block = int(cfg.get("block", 128))
         self.num_keep = int(cfg.get("num_keep", 32))
         if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
@@ -287,27 +331,53 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self._per_head_cache[key] = (value, value._version, out)
         return out
 
-    def _mask_rule(self, B, H, nb, device):
-        """The ops.MaskRule of a call, or None when the options are the scalar energy rule's."""
+    def _judge_rows(self, device):
+        r = self.judge_rows
+        if r.device != device or r.dtype != torch.int32:
+            r = r.to(device=device, dtype=torch.int32)
+            self.judge_rows = r
+        return r
+
+    def _judge_budget(self, q, k, nb, judge_rows=None):
+        """head_budget="judge": this call's per-head max_keep counts, int32 [B,H] on the device, from
+        the estimator on the q and k received (caller row order). Two launches for the estimator and
+        one for the budget rule, all on the current stream, before the predictor's."""
+        rows = self._judge_rows(q.device) if judge_rows is None else judge_rows
+        sparsity = ops.judge_sparsity(q, k, rows, key_stride=self.judge_key_stride, top=self.judge_top)
+        budget = ops.head_budget(sparsity, nb, self.max_retain_ratio, self.judge_clamp, self.variant)
+        self.last_head_sparsity, self.last_head_budget = sparsity, budget
+        return budget
+
+    def _mask_rule(self, B, H, nb, device, max_keep=None):
+        """The ops.MaskRule of a call, or None when the options are the scalar energy rule's.
+        ``max_keep``: the judge's int32 [B,H] counts, in place of max_retain_ratio's."""
         if self.mask_mode == "topk":
             k0 = int(nb * self.init_k) if self.init_k < 1 else int(self.init_k)
             return ops.MaskRule(mode="topk", init_k=k0)
         per_head = {n: v for n, v in (("min_keep", self.min_retain_ratio), ("max_keep", self.max_retain_ratio),
                                       ("energy_threshold", self.energy_threshold))
                     if isinstance(v, torch.Tensor)}
-        if not per_head:
+        if not per_head and max_keep is None:
             return None
         names = {"min_keep": "min_retain_ratio", "max_keep": "max_retain_ratio",
                  "energy_threshold": "energy_threshold"}
-        return ops.MaskRule(mode="energy", **{n: self._per_head(names[n], v, B, H, nb, device)
-                                              for n, v in per_head.items()})
+        fields = {n: self._per_head(names[n], v, B, H, nb, device) for n, v in per_head.items()}
+        if max_keep is not None:
+            fields["max_keep"] = max_keep
+        return ops.MaskRule(mode="energy", **fields)
 
     # -------------------------------------------------------------------------------- forward
     def predict_mask(self, q, k, q_off=None, k_off=None, count=None, staged_event=None, pool=None,
-                     rows_kept=None):
+                     rows_kept=None, judge_rows=None):
         """Block mask [B,H,nb,nb] (uint8, Gilbert order) and normalised pooled scores. ``pool``
-        (v, gap, outs) runs the pooled K/V pass inside the score kernel's launch."""
+        (v, gap, outs) runs the pooled K/V pass inside the score kernel's launch. ``judge_rows``
+        overrides the module's probe rows for this call (head_budget="judge")."""
         B, H, L, D = q.shape
+        # the judge's workspace is allocated (and its launches enqueued) before the predictor's
+        # temporaries exist
+        budget = None
+        if self.head_budget == "judge":
+            budget = self._judge_budget(q, k, (L + self.block - 1) // self.block, judge_rows)
         rand = philox = None
         if q_off is None and k_off is None:
             # the reference's two draws (:77-78, q first), generated and ranked inside the sampling
@@ -321,7 +391,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
         elif k_off is None:
             k_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
         nb = (L + self.block - 1) // self.block
-        rule = self._mask_rule(B, H, nb, q.device)
+        rule = self._mask_rule(B, H, nb, q.device, budget)
         if rule is not None:
             # scalars of the options given as tensors are placeholders the rule's arrays replace
             thr = 0.95 if isinstance(self.energy_threshold, torch.Tensor) else self.energy_threshold
@@ -343,7 +413,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
 
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *,
                 q_off: Optional[torch.Tensor] = None, k_off: Optional[torch.Tensor] = None,
-                block_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                block_mask: Optional[torch.Tensor] = None,
+                judge_rows=None) -> torch.Tensor:
         B, H, L, D = q.shape
         if k.shape != q.shape or v.shape != q.shape:
             # the reference's index_select over the Gilbert index fails on a shorter k/v (e.g. the
@@ -374,7 +445,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
             with torch.no_grad():
                 _, mask = self.predict_mask(q.detach(), k.detach(), q_off, k_off, count,
                                             pool=(v, self.sample_gap, outs) if ride else None,
-                                            rows_kept=rows_kept)
+                                            rows_kept=rows_kept, judge_rows=judge_rows)
             if ride:
                 pooled = outs
             elif fused:

@@ -698,6 +698,98 @@ def block_mask_rule(po, rule=None, *, energy_threshold=0.95, min_keep=1, max_kee
     return mask
 
 
+# ----------------------------------------------------------------------------------------------
+# head-adaptive retain budgets
+# ----------------------------------------------------------------------------------------------
+JUDGE_MAX_SAMPLES = _lib.VB_JUDGE_MAX_SAMPLES
+BUDGET_ARITH = {"cog": 0, "wan": 1}   # attention.retain_counts' two arithmetics
+
+
+def judge_rows(rows, L: int, dev) -> torch.Tensor:
+    """The probe rows of judge_sparsity as a device int32 [S] tensor. A host-side ``rows`` (list,
+    tuple or numpy array) is range-checked against [0, L) here; a device tensor cannot be checked
+    without a synchronisation and is clamped to [0, L-1] by the kernel instead."""
+    if isinstance(rows, torch.Tensor):
+        if rows.dim() != 1:
+            raise ValueError(f"judge_sparsity: rows must be one-dimensional, got {tuple(rows.shape)}")
+        if rows.is_cuda:
+            _check_dev("judge_sparsity: rows", rows, dev)
+            return rows.to(torch.int32).contiguous()
+        rows = rows.numpy()
+    r = np.asarray(rows)
+    if r.ndim != 1 or r.size == 0 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("judge_sparsity: rows must be a non-empty one-dimensional list of integers")
+    if r.min() < 0 or r.max() >= L:
+        raise ValueError(f"judge_sparsity: rows must lie in [0, {L}), got [{r.min()}, {r.max()}]")
+    return torch.from_numpy(r.astype(np.int32)).to(dev)
+
+
+def judge_sparsity(q, k, rows, *, key_stride: int = 3, top: float = 0.2, scale=None, want_rows: bool = False):
+    """vb_judge_sparsity: the reference's judge_sparsity(q, k) on the device. q,k [B,H,L,D] (strided
+    views are read in place); ``rows`` the S <= 64 sampled query rows (a device int32 tensor, or a
+    host list / numpy array, which is range-checked), shared by every (b,h). Per sampled row: the
+    softmax over every ``key_stride``-th key, and the mass of its top_n = int(n * top) largest
+    entries (n = ceil(L / key_stride)); the result is the mean over the rows, fp32 [B,H]. With
+    ``want_rows`` also the per-row masses, fp32 [B,H,S]."""
+    if k.shape != q.shape or q.dim() != 4:
+        raise ValueError(f"judge_sparsity: q and k must share a [B,H,L,D] shape, got {tuple(q.shape)} "
+                         f"and {tuple(k.shape)}")
+    dev = _require_gpu(q, k)
+    B, H, L, D = q.shape
+    key_stride = int(key_stride)
+    if key_stride < 1:
+        raise ValueError(f"judge_sparsity: key_stride must be >= 1, got {key_stride}")
+    n = (L + key_stride - 1) // key_stride
+    top_n = int(n * top)
+    if not 1 <= top_n <= n:
+        raise ValueError(f"judge_sparsity: int(n * top) = {top_n} must lie in [1, n = {n}]")
+    rows = judge_rows(rows, L, dev)
+    S = rows.numel()
+    if not 1 <= S <= JUDGE_MAX_SAMPLES:
+        raise ValueError(f"judge_sparsity: 1 to {JUDGE_MAX_SAMPLES} sampled rows, got {S}")
+    a = _lib.JudgeArgs()
+    a.B, a.H, a.L, a.D, a.S = B, H, L, D, S
+    a.key_stride, a.top_n = key_stride, top_n
+    a.scale = float(scale) if scale else 0.0
+    a.dtype = _dtype_code(q)
+    lib = _lib.load()
+    nbytes = int(lib.vb_judge_sparsity_workspace_size(ctypes.byref(a)))
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    q, k = _aligned_bhld(q), _aligned_bhld(k)
+    sparsity = torch.empty(B, H, device=dev, dtype=torch.float32)
+    row_mass = torch.empty(B, H, S, device=dev, dtype=torch.float32) if want_rows else None
+    a.q, a.k = q.data_ptr(), k.data_ptr()
+    a.q_stride, a.k_stride = _s3(q), _s3(k)
+    a.rows = rows.data_ptr()
+    a.sparsity, a.row_mass = sparsity.data_ptr(), _ptr(row_mass)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    check(lib.vb_judge_sparsity(ctypes.byref(a), _stream(dev)), "vb_judge_sparsity")
+    return (sparsity, row_mass) if want_rows else sparsity
+
+
+def head_budget(sparsity, nb: int, base: float, clamp=(0.05, 0.9), variant: str = "cog", want_ratio: bool = False):
+    """vb_head_budget: judge_sparsity's fp32 [B,H] -> kept-block counts int32 [B,H] (a MaskRule's
+    ``max_keep``): ratio = clamp(base * sparsity / sparsity.mean(), *clamp) in float64, the mean over
+    batch and heads together, and count = max(1, int(nb * ratio)) in ``variant``'s arithmetic
+    (attention.retain_counts). With ``want_ratio`` also the ratios, fp32 [B,H]."""
+    if variant not in BUDGET_ARITH:
+        raise ValueError(f"head_budget: variant must be one of {list(BUDGET_ARITH)}, got {variant!r}")
+    lo, hi = float(clamp[0]), float(clamp[1])
+    if not lo <= hi:
+        raise ValueError(f"head_budget: clamp needs lo <= hi, got ({lo}, {hi})")
+    dev = _require_gpu(sparsity)
+    if sparsity.dim() != 2 or sparsity.dtype != torch.float32:
+        raise ValueError(f"head_budget: sparsity must be fp32 [B,H], got {sparsity.dtype} {tuple(sparsity.shape)}")
+    sparsity = sparsity.contiguous()
+    B, H = sparsity.shape
+    keep = torch.empty(B, H, device=dev, dtype=torch.int32)
+    ratio = torch.empty(B, H, device=dev, dtype=torch.float32) if want_ratio else None
+    check(_lib.load().vb_head_budget(sparsity.data_ptr(), B, H, int(nb), float(base), lo, hi,
+                                     BUDGET_ARITH[variant], keep.data_ptr(), _ptr(ratio), _stream(dev)),
+          "vb_head_budget")
+    return (keep, ratio) if want_ratio else keep
+
+
 def pool_kv_outputs(k, gap: int, reordered: bool = False):
     """Allocate pool_kv's outputs (kp, vp[, k_r, v_r]) on the current stream. A caller that launches
     pool_kv on a side stream allocates them BEFORE enqueueing other work whose temporaries could
