@@ -247,3 +247,319 @@ def test_gilbert_rearranger_round_trip_cpu():
     q, k, v = g.rearrange(x, x, x)
     assert torch.equal(q[..., -10:, :], x[..., :10, :])
     assert torch.equal(g.reversed_rearrange(q), x)
+
+
+# ---------------------------------------------------------------------------------------------
+# The attention entries' argument validation and workspace arithmetic, pinned value by value. Every
+# case below is refused by a host check, so nothing is launched and the fake (non-null, 16-byte
+# aligned) pointers are never dereferenced. The literals were recorded from the library before the
+# backward's host layer moved into a unit of its own: a refactor of that layer must reproduce them.
+# ---------------------------------------------------------------------------------------------
+_PTR, _WS = 1 << 20, 1 << 24
+_B, _H, _L, _LK, _LKP, _GAP, _D = 1, 2, 200, 330, 42, 8, 64
+_BIG = 1 << 62
+
+
+def _st(L, D=_D, H=_H):
+    return (H * L * D, L * D, D)
+
+
+def _fwd_args():
+    from vblade import _lib
+    a = _lib.AttnArgs()
+    a.q = a.k = a.v = a.out = a.kp = a.vp = _PTR
+    a.q_stride = a.out_stride = _st(_L)
+    a.k_stride = a.v_stride = _st(_LK)
+    a.kp_stride = a.vp_stride = _st(_LKP)
+    a.use_main, a.Lkp = 1, _LKP
+    a.B, a.H, a.Lq, a.Lk, a.D = _B, _H, _L, _LK, _D
+    return a
+
+
+def _ml_fwd_args():
+    from vblade import _lib
+    a = _lib.MlAttnArgs()
+    a.q = a.kpyr = a.vpyr = a.level_mask = a.out = _PTR
+    a.q_stride = a.out_stride = _st(_L)
+    a.B, a.H, a.L, a.D = _B, _H, _L, _D
+    return a
+
+
+def _bwd_args():
+    from vblade import _lib
+    a = _lib.BwdArgs()
+    a.q = a.k = a.v = a.out = a.lse = a.dout = a.dq = a.dk = a.dv = _PTR
+    a.kp = a.vp = a.out2 = a.lse2 = _PTR
+    a.q_stride = a.out_stride = a.out2_stride = a.dout_stride = a.dq_stride = _st(_L)
+    a.k_stride = a.v_stride = a.dk_stride = a.dv_stride = _st(_LK)
+    a.kp_stride = a.vp_stride = _st(_LKP)
+    a.Lkp, a.pool_gap = _LKP, _GAP
+    a.B, a.H, a.Lq, a.Lk, a.D = _B, _H, _L, _LK, _D
+    a.workspace, a.workspace_bytes = _WS, _BIG
+    return a
+
+
+def _ml_bwd_args():
+    from vblade import _lib
+    a = _lib.MlBwdArgs()
+    a.q = a.kpyr = a.vpyr = a.level_mask = a.out = a.lse = a.dout = a.dq = a.dk = a.dv = _PTR
+    a.q_stride = a.out_stride = a.dout_stride = a.dq_stride = a.dk_stride = a.dv_stride = _st(_L)
+    a.B, a.H, a.L, a.D = _B, _H, _L, _D
+    a.workspace, a.workspace_bytes = _WS, _BIG
+    return a
+
+
+# vb_block_sparse_attn_bwd's positional arguments, by name
+_BS_NAMES = ("dout", "q", "k", "v", "out", "lse", "cu_q", "cu_k", "head_mask_type", "streaming_info",
+             "mask", "batch", "num_heads", "head_dim", "max_seqlen_q", "max_seqlen_k", "p_dropout",
+             "softmax_scale", "is_causal", "exact_streaming", "deterministic", "dtype", "dq", "dk", "dv",
+             "workspace", "workspace_bytes", "mask_head_mode", "stream")
+
+
+def _bs_bwd_args():
+    a = dict.fromkeys(_BS_NAMES, None)
+    for n in ("dout", "q", "k", "v", "out", "lse", "cu_q", "cu_k", "dq", "dk", "dv"):
+        a[n] = _PTR
+    a.update(batch=_B, num_heads=_H, head_dim=_D, max_seqlen_q=_L, max_seqlen_k=_LK, p_dropout=0.0,
+             softmax_scale=0.0, is_causal=0, exact_streaming=0, deterministic=1, dtype=0,
+             workspace=_WS, workspace_bytes=_BIG, mask_head_mode=0)
+    return a
+
+
+def _set(**kw):
+    def f(a):
+        for k, v in kw.items():
+            if isinstance(a, dict):
+                a[k] = v
+            else:
+                setattr(a, k, v)
+    return f
+
+
+def _row_stride(field, value):
+    def f(a):
+        s = list(getattr(a, field))
+        s[2] = value
+        setattr(a, field, tuple(s))
+    return f
+
+
+def _both(*fs):
+    def f(a):
+        for g in fs:
+            g(a)
+    return f
+
+
+def _short_ws(size_fn):
+    """One byte less than the entry's own size function asks for (never a guessed figure: a size that
+    passed the check would launch on the fake pointers)."""
+    def f(a):
+        from vblade import _lib
+        fn = getattr(_lib.load(), size_fn)
+        if isinstance(a, dict):
+            a["workspace_bytes"] = fn(a["batch"], a["num_heads"], a["max_seqlen_q"]) - 1
+        else:
+            a.workspace_bytes = fn(ctypes.byref(a)) - 1
+    return f
+
+
+_INV, _UNS = -1, -2
+_TOO_LONG = 1025 * 128
+# (entry, fault, mutation, return code, vb_last_error())
+_REJECTIONS = [
+    ("vb_attn_fwd", "null tensor", _set(out=None), _INV, "vb_attn_fwd: missing q/k/v/out"),
+    ("vb_attn_fwd", "D=96", _set(D=96), _UNS, "attn: head_dim must be 64 or 128, got 96"),
+    ("vb_attn_fwd", "dtype 7", _set(dtype=7), _INV, "attn: unknown dtype"),
+    ("vb_attn_fwd", "stride of 4", _set(k_stride=(4, 4, 4)), _INV,
+     "vb_attn_fwd: k/v strides must be multiples of 8 elements"),
+    ("vb_attn_fwd", "pointer off by 8", _set(v=_PTR + 8), _INV, "vb_attn_fwd: tensors must be 16-byte aligned"),
+    ("vb_attn_fwd", "row stride 2^24", _row_stride("k_stride", 1 << 23), _UNS,
+     "vb_attn_fwd: k/v/kp/vp row strides must be < 2^24 bytes"),
+    ("vb_attn_fwd", "slice >= 2 GiB", _row_stride("v_stride", 1 << 22), _UNS,
+     "vb_attn_fwd: a k/v (b,h) slice spans >= 2 GiB"),
+    ("vb_attn_fwd", "pooled slice >= 2 GiB", _both(_set(Lkp=330), _row_stride("kp_stride", 1 << 22)), _UNS,
+     "vb_attn_fwd: a kp/vp (b,h) slice spans >= 2 GiB"),
+    ("vb_attn_fwd", "1025 blocks", _set(Lk=_TOO_LONG), _UNS, "vb_attn_fwd: Lk too long"),
+    ("vb_attn_fwd", "pooled without vp", _set(vp=None), _INV, "vb_attn_fwd: pooled branch needs vp and Lkp > 0"),
+    ("vb_attn_fwd", "D=96 and dtype 7", _set(D=96, dtype=7), _INV, "attn: unknown dtype"),
+
+    ("vb_ml_attn_fwd", "null tensor", _set(level_mask=None), _INV,
+     "vb_ml_attn_fwd: missing q/kpyr/vpyr/level_mask/out"),
+    ("vb_ml_attn_fwd", "D=96", _set(D=96), _UNS, "vb_ml_attn_fwd: head_dim must be 64 or 128, got 96"),
+    ("vb_ml_attn_fwd", "dtype 7", _set(dtype=7), _INV, "vb_ml_attn_fwd: unknown dtype"),
+    ("vb_ml_attn_fwd", "stride of 4", _set(out_stride=(4, 4, 4)), _INV,
+     "vb_ml_attn_fwd: q/out strides must be multiples of 8 elements"),
+    ("vb_ml_attn_fwd", "pointer off by 8", _set(kpyr=_PTR + 8), _INV,
+     "vb_ml_attn_fwd: tensors must be 16-byte aligned"),
+    ("vb_ml_attn_fwd", "1025 blocks", _set(L=_TOO_LONG), _UNS, "vb_ml_attn_fwd: L too long"),
+
+    ("vb_attn_bwd", "null tensor", _set(dv=None), _INV, "vb_attn_bwd: missing tensor"),
+    ("vb_attn_bwd", "D=96", _set(D=96), _UNS, "vb_attn_bwd: head_dim must be 64 or 128, got 96"),
+    ("vb_attn_bwd", "dtype 7", _set(dtype=7), _INV, "vb_attn_bwd: unknown dtype"),
+    ("vb_attn_bwd", "stride of 4", _set(dk_stride=(4, 4, 4)), _INV,
+     "vb_attn_bwd: strides must be multiples of 8 elements"),
+    ("vb_attn_bwd", "pooled stride of 4", _set(out2_stride=(4, 4, 4)), _INV,
+     "vb_attn_bwd: strides must be multiples of 8 elements"),
+    ("vb_attn_bwd", "pointer off by 8", _set(dout=_PTR + 8), _INV, "vb_attn_bwd: tensors must be 16-byte aligned"),
+    ("vb_attn_bwd", "pooled pointer off by 8", _set(vp=_PTR + 8), _INV,
+     "vb_attn_bwd: tensors must be 16-byte aligned"),
+    ("vb_attn_bwd", "row stride 2^24", _row_stride("k_stride", 1 << 24), _UNS,
+     "vb_attn_bwd: a k/v/kp/vp (b,h) slice spans >= 2 GiB"),
+    ("vb_attn_bwd", "q slice >= 2 GiB", _row_stride("dout_stride", 1 << 23), _UNS,
+     "vb_attn_bwd: a q/dout (b,h) slice spans >= 2 GiB"),
+    ("vb_attn_bwd", "k slice >= 2 GiB", _row_stride("v_stride", 1 << 22), _UNS,
+     "vb_attn_bwd: a k/v/kp/vp (b,h) slice spans >= 2 GiB"),
+    ("vb_attn_bwd", "1025 blocks", _set(Lq=_TOO_LONG), _UNS, "vb_attn_bwd: sequence too long"),
+    ("vb_attn_bwd", "unknown kernel_select bit", _set(kernel_select=8), _INV,
+     "vb_attn_bwd: unknown kernel_select bits"),
+    ("vb_attn_bwd", "missing workspace", _set(workspace=None), _INV,
+     "vb_attn_bwd: workspace missing or smaller than vb_attn_bwd_workspace_size()"),
+    ("vb_attn_bwd", "short workspace", _short_ws("vb_attn_bwd_workspace_size"), _INV,
+     "vb_attn_bwd: workspace missing or smaller than vb_attn_bwd_workspace_size()"),
+    ("vb_attn_bwd", "pooled without vp", _set(vp=None), _INV,
+     "vb_attn_bwd: pooled branch needs vp, Lkp, out2, lse2 and pool_gap"),
+    ("vb_attn_bwd", "Lkp * gap < Lk", _set(pool_gap=7), _INV, "vb_attn_bwd: Lkp * pool_gap must cover Lk"),
+    ("vb_attn_bwd", "D=96 and dtype 7", _set(D=96, dtype=7), _UNS,
+     "vb_attn_bwd: head_dim must be 64 or 128, got 96"),
+    ("vb_attn_bwd", "stride of 4 and pointer off by 8", _set(q_stride=(4, 4, 4), q=_PTR + 8), _INV,
+     "vb_attn_bwd: strides must be multiples of 8 elements"),
+    ("vb_attn_bwd", "short workspace and slice >= 2 GiB",
+     _both(_short_ws("vb_attn_bwd_workspace_size"), _row_stride("k_stride", 1 << 22)), _INV,
+     "vb_attn_bwd: workspace missing or smaller than vb_attn_bwd_workspace_size()"),
+
+    ("vb_block_sparse_attn_bwd", "null tensor", _set(cu_k=None), _INV, "vb_block_sparse_attn_bwd: null tensor"),
+    ("vb_block_sparse_attn_bwd", "D=96", _set(head_dim=96), _UNS,
+     "vb_block_sparse_attn_bwd: head_dim must be 64 or 128"),
+    ("vb_block_sparse_attn_bwd", "dtype 7", _set(dtype=7), _INV, "vb_block_sparse_attn_bwd: unknown dtype"),
+    ("vb_block_sparse_attn_bwd", "pointer off by 8", _set(dk=_PTR + 8), _INV,
+     "vb_block_sparse_attn_bwd: tensors must be 16-byte aligned"),
+    ("vb_block_sparse_attn_bwd", "q slice >= 2 GiB", _set(num_heads=1 << 17), _UNS,
+     "vb_block_sparse_attn_bwd: a sequence's q/dout span >= 2 GiB"),
+    ("vb_block_sparse_attn_bwd", "k slice >= 2 GiB", _set(num_heads=1 << 16), _UNS,
+     "vb_block_sparse_attn_bwd: a sequence's k/v span >= 2 GiB"),
+    ("vb_block_sparse_attn_bwd", "1025 blocks", _set(max_seqlen_k=_TOO_LONG), _UNS,
+     "vb_block_sparse_attn_bwd: sequence too long"),
+    ("vb_block_sparse_attn_bwd", "missing workspace", _set(workspace=None), _INV,
+     "vb_block_sparse_attn_bwd: workspace missing or too small"),
+    ("vb_block_sparse_attn_bwd", "short workspace", _short_ws("vb_block_sparse_attn_bwd_workspace_size"), _INV,
+     "vb_block_sparse_attn_bwd: workspace missing or too small"),
+
+    ("vb_ml_attn_bwd", "null tensor", _set(lse=None), _INV, "vb_ml_attn_bwd: missing tensor"),
+    ("vb_ml_attn_bwd", "D=96", _set(D=96), _UNS, "vb_ml_attn_bwd: head_dim must be 64 or 128, got 96"),
+    ("vb_ml_attn_bwd", "dtype 7", _set(dtype=7), _INV, "vb_ml_attn_bwd: unknown dtype"),
+    ("vb_ml_attn_bwd", "stride of 4", _set(dq_stride=(4, 4, 4)), _INV,
+     "vb_ml_attn_bwd: strides must be multiples of 8 elements"),
+    ("vb_ml_attn_bwd", "pointer off by 8", _set(vpyr=_PTR + 8), _INV,
+     "vb_ml_attn_bwd: tensors must be 16-byte aligned"),
+    ("vb_ml_attn_bwd", "slice >= 2 GiB", _row_stride("q_stride", 1 << 23), _UNS,
+     "vb_ml_attn_bwd: a q/dout (b,h) slice spans >= 2 GiB"),
+    ("vb_ml_attn_bwd", "1025 blocks", _set(L=_TOO_LONG), _UNS, "vb_ml_attn_bwd: sequence too long"),
+    ("vb_ml_attn_bwd", "unknown kernel_select bit", _set(kernel_select=8), _INV,
+     "vb_ml_attn_bwd: unsupported kernel_select bits (the multi-level dQ has one ring)"),
+    ("vb_ml_attn_bwd", "VB_BWD_SEL_DQ_RING4", _set(kernel_select=4), _INV,
+     "vb_ml_attn_bwd: unsupported kernel_select bits (the multi-level dQ has one ring)"),
+    ("vb_ml_attn_bwd", "missing workspace", _set(workspace=None), _INV,
+     "vb_ml_attn_bwd: workspace missing or smaller than vb_ml_attn_bwd_workspace_size()"),
+    ("vb_ml_attn_bwd", "short workspace", _short_ws("vb_ml_attn_bwd_workspace_size"), _INV,
+     "vb_ml_attn_bwd: workspace missing or smaller than vb_ml_attn_bwd_workspace_size()"),
+]
+_VALID = {"vb_attn_fwd": _fwd_args, "vb_ml_attn_fwd": _ml_fwd_args, "vb_attn_bwd": _bwd_args,
+          "vb_block_sparse_attn_bwd": _bs_bwd_args, "vb_ml_attn_bwd": _ml_bwd_args}
+
+
+def _call(lib, entry, a):
+    if isinstance(a, dict):
+        return getattr(lib, entry)(*(a[n] for n in _BS_NAMES))
+    return getattr(lib, entry)(ctypes.byref(a), None)
+
+
+@pytest.mark.parametrize("entry,fault,mutate,code,message", _REJECTIONS,
+                         ids=[f"{e}-{f}".replace(" ", "_") for e, f, *_ in _REJECTIONS])
+def test_attention_entries_reject_one_fault_at_a_time(lib, entry, fault, mutate, code, message):
+    a = _VALID[entry]()
+    mutate(a)
+    rc = _call(lib, entry, a)
+    got = lib.vb_last_error().decode()
+    print(f"{entry} [{fault}]: {rc} {got!r}")
+    assert (rc, got) == (code, message)
+
+
+# vb_attn_bwd_workspace_size at B=1, H=2: (Lq, Lk, D, q_rows, pooled) -> bytes; pooled Lkp = ceil(Lk / 8)
+_BWD_WS = {
+    (128, 128, 64, False, False): 4096,
+    (128, 128, 64, False, True): 20480,
+    (128, 128, 64, True, False): 69632,
+    (128, 128, 64, True, True): 86016,
+    (128, 128, 128, False, False): 4096,
+    (128, 128, 128, False, True): 36864,
+    (128, 128, 128, True, False): 135168,
+    (128, 128, 128, True, True): 167936,
+    (200, 330, 64, False, False): 8192,
+    (200, 330, 64, False, True): 137216,
+    (200, 330, 64, True, False): 110592,
+    (200, 330, 64, True, True): 239616,
+    (200, 330, 128, False, False): 8192,
+    (200, 330, 128, False, True): 266240,
+    (200, 330, 128, True, False): 212992,
+    (200, 330, 128, True, True): 471040,
+    (1000, 1000, 64, False, False): 32768,
+    (1000, 1000, 64, False, True): 1184768,
+    (1000, 1000, 64, True, False): 544768,
+    (1000, 1000, 64, True, True): 1696768,
+    (1000, 1000, 128, False, False): 32768,
+    (1000, 1000, 128, False, True): 2336768,
+    (1000, 1000, 128, True, False): 1056768,
+    (1000, 1000, 128, True, True): 3360768,
+}
+_BS_BWD_WS = 24576   # vb_block_sparse_attn_bwd_workspace_size(2, 3, 200)
+# vb_ml_attn_bwd_workspace_size at B=1, H=2: (L, D, rows) -> bytes
+_ML_BWD_WS = {
+    (200, 64, False): 237568,
+    (200, 64, True): 339968,
+    (200, 128, False): 466944,
+    (200, 128, True): 671744,
+    (384, 64, False): 356352,
+    (384, 64, True): 552960,
+    (384, 128, False): 700416,
+    (384, 128, True): 1093632,
+}
+
+
+def _bwd_ws_cases():
+    return [(lq, lk, d, rows, pooled) for lq, lk in ((128, 128), (200, 330), (1000, 1000))
+            for d in (64, 128) for rows in (False, True) for pooled in (False, True)]
+
+
+def _ml_bwd_ws_cases():
+    return [(L, d, rows) for L in (200, 384) for d in (64, 128) for rows in (False, True)]
+
+
+def _bwd_ws(lib, lq, lk, d, rows, pooled):
+    from vblade import _lib
+    a = _lib.BwdArgs()
+    a.B, a.H, a.Lq, a.Lk, a.D = _B, _H, lq, lk, d
+    a.q_rows = _PTR if rows else None
+    if pooled:
+        a.kp, a.Lkp = _PTR, (lk + 7) // 8
+    return lib.vb_attn_bwd_workspace_size(ctypes.byref(a))
+
+
+def _ml_bwd_ws(lib, L, d, rows):
+    from vblade import _lib
+    a = _lib.MlBwdArgs()
+    a.B, a.H, a.L, a.D = _B, _H, L, d
+    a.rows = _PTR if rows else None
+    return lib.vb_ml_attn_bwd_workspace_size(ctypes.byref(a))
+
+
+def test_backward_workspace_sizes_are_pinned(lib):
+    """psplit = 1 at Lq = 128 (one q-block) and > 1 at the longer ones (2 and 8 q-range partials)."""
+    assert set(_BWD_WS) == set(_bwd_ws_cases()) and set(_ML_BWD_WS) == set(_ml_bwd_ws_cases())
+    got = {c: _bwd_ws(lib, *c) for c in _bwd_ws_cases()}
+    print(got)
+    assert got == _BWD_WS
+    assert lib.vb_block_sparse_attn_bwd_workspace_size(2, 3, 200) == _BS_BWD_WS
+    got = {c: _ml_bwd_ws(lib, *c) for c in _ml_bwd_ws_cases()}
+    print(got)
+    assert got == _ML_BWD_WS

@@ -1,20 +1,22 @@
 #!/usr/bin/env python3
-"""Kernel-by-kernel comparison of two device listings of a predictor unit (a refactor check: does the
-GPU still execute the same instructions?). No GPU needed.
+"""Kernel-by-kernel comparison of two device listings of any unit under video-blade_amd/csrc (a
+refactor check: does the GPU still execute the same instructions?). No GPU needed.
 
-Produce a listing of a unit (vb_predict.hip or vb_predict_rule.hip) with the Makefile's flags for it:
+Produce a listing of the unit with the Makefile's flags for that file, e.g. for the predictor
 
   hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Ivideo-blade_amd/csrc \\
         -fno-honor-nans --cuda-device-only -S video-blade_amd/csrc/vb_predict.hip -o new.s
 
+(vb_attn_bwd.hip: -mllvm -amdgpu-sched-strategy=iterative-ilp; vb_attn_bwd_kv.hip:
+-fno-slp-vectorize; vb_attn_fwd.hip: -fno-slp-vectorize -fno-honor-nans and the scheduler flag),
 then, with old.s made the same way at the commit to compare against:
 
-  python tools/diag/pred_listing_diff.py old.s new.s            # expects no differing line
-  python tools/diag/pred_listing_diff.py old.s new.s --kernarg  # a PredParams field went or came
+  python tools/diag/listing_diff.py old.s new.s            # expects no differing line
+  python tools/diag/listing_diff.py old.s new.s --kernarg  # a kernel-argument field went or came
 
 Per kernel the instruction stream with its .amdhsa_kernel descriptor and its metadata entry (VGPR,
 SGPR, LDS and scratch sizes) are compared line for line after normalising three things only: the
-score kernel's mangled name (its template arguments become <D,T,long,keep,rule>, whatever further
+predictor score kernel's mangled name (its template arguments become <D,T,long,keep,rule>, whatever further
 bool parameters a side has), the ordinal that local labels take from the kernel's place in the unit
 (.LBB<n>_<m> and BB<n>_<m> in loop comments, .Lfunc_end<n>, .Lpost_getpc<n>; the blanks in front of
 a label's comment, which move with the ordinal's width, count as one) and .file/.ident lines. With --kernarg, lines that differ only in a kernel-argument size or offset (the

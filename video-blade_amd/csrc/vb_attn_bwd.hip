@@ -31,11 +31,9 @@
 //                       dQ^T += K^T.dS^T                (A = transposed read of the K tile)
 // No atomics: every gradient element is written by exactly one workgroup, so results are
 // bit-reproducible run to run (the reference's deterministic=True).
-#include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
+#include "vb_args.hpp"
 #include "vb_attn_bwd.hpp"
 
 namespace vb {
@@ -118,37 +116,15 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(const PrepParams p) {
 // ------------------------------------------------------------------------------------------------
 // dK / dV: one workgroup per (b, h, 128-key block)
 // ------------------------------------------------------------------------------------------------
-#ifndef VB_BWD_SEED128
-#define VB_BWD_SEED128 0    // D=128: dP seeded with -Delta too (measured 6 % slower on Wan's dK/dV)
-#endif
-#ifndef VB_DKDV_PRIO64
-#define VB_DKDV_PRIO64 1   // measured (cog backward): 1 1.013x, 3 1.009x
-#endif
-#ifndef VB_DKDV_PRIO128
-#define VB_DKDV_PRIO128 0  // one wave per SIMD at D=128: nothing to arbitrate
-#endif
-#ifndef VB_DKDV_WAVES_D64
-#define VB_DKDV_WAVES_D64 2   // waves per SIMD the D=64 dK/dV kernel is register-budgeted for
-#endif
-#ifndef VB_ML_PYR_WAVES
-// waves per multi-level pooled dK/dV workgroup at D=64: 2 = 64-row items on a 2-slot ring, four
-// workgroups per CU (vb_ml_attn_bwd 1.15x over 4 = 128-row items, dk bit-identical;
-// profiles/archive/r05_ml_bwd_pyr2_ab.log). D=128 keeps 4 (two waves spill there).
-#define VB_ML_PYR_WAVES 2
-#endif
-#ifndef VB_ML_LONG_FIRST
-#define VB_ML_LONG_FIRST 1   // multi-level pooled dK/dV items in level 8, 4, 2 order (longest first; 0: 2, 4, 8)
-#endif
 // kW: waves per workgroup (4, or 2 for the multi-level pooled items: an item is 32 kW pyramid rows,
 // so a level-2 item covers one key block and walks its own q-list instead of a union, and a level-4
 // or level-8 item half as many blocks; the union walk leaves fewer waves idle).
 template <int D, class T, bool kPooled, bool kML = false, int kW = 4>
-__global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd_dkdv_kernel(const BwdParams p) {
+__global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : bwd::kDkdvWavesD64) bwd_dkdv_kernel(const BwdParams p) {
   using namespace bwd;
   static_assert(kW == 4 || (kML && kPooled), "2-wave workgroups: the multi-level pooled items only");
   constexpr int kRows = 32 * kW;             // keys (pyramid rows) per work item
-  // s_setprio 1 around the MFMA chains (bit 0: S and dP, bit 1: the dV/dK steps)
-  constexpr int kPrioKV = D == 128 ? VB_DKDV_PRIO128 : VB_DKDV_PRIO64;
+  constexpr int kPrioKV = D == 128 ? kDkdvPrio128 : kDkdvPrio64;
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
   constexpr int RB = D * 2;                 // bytes per row
@@ -173,17 +149,10 @@ __global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd
 
   const int BH = p.B * p.H;
   const int nkb = kPooled ? p.nbkp : p.nbk;
-  // pooled-key blocks see every q-block: their work is split into psplit q-block ranges (split
-  // innermost, so a key block's workgroups run together); main blocks XCD-contiguous
-  // Main blocks: the `heavy_rows` last key blocks of every head (CogVideoX's forced dense text
-  // columns, kept by every q-block: ~8x the average column's tiles) go first over all XCDs, then
-  // each XCD takes a contiguous head-major range with key blocks in descending order. Ascending
-  // order put every head's two heavy columns at the end of its range, so the last head of each
-  // XCD's range left a long tail (measured: 1.26 waves per SIMD on average at 2 possible).
   const int split = kPooled ? (int)blockIdx.x % p.psplit : 0;
   int bh, kblk;
   int ml_e = 0, ml_m = 0;   // multi-level pooled items: level exponent and pyramid block
-  if (kML && kPooled && VB_ML_LONG_FIRST) {
+  if (kML && kPooled) {
     // longest items first: a level-8 block's q-list is the union over 8 key blocks (≈4x a level-2
     // item's tiles), so level 8, then 4, then 2, each spread over the heads (consecutive
     // workgroups = different heads, so different XCDs); placement only, the results are the same
@@ -194,44 +163,21 @@ __global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd
     bh = lin % BH;
     ml_m = lin / BH;
     kblk = 0;
-  } else if (kPooled) {
-    const int lin = (int)blockIdx.x / p.psplit;
-    bh = lin / nkb;
-    kblk = lin % nkb;
   } else {
-    const int hr = kML ? 0 : min(p.heavy_rows, nkb);
-    const int n_heavy = hr * BH;
-    if ((int)blockIdx.x < n_heavy) {
-      kblk = nkb - 1 - (int)(blockIdx.x / BH);
-      bh = blockIdx.x % BH;
-    } else {
-      const int cols_left = nkb - hr;
-      const int lin = xcd_linear(blockIdx.x - n_heavy, cols_left * BH);
-      bh = lin / cols_left;
-      kblk = cols_left - 1 - lin % cols_left;
-    }
+    dkdv_item<kPooled, kML>(p, BH, nkb, bh, kblk);
   }
   const int b = bh / p.H, h = bh % p.H;
 
-  int Lq = p.Lq, Lk = p.Lk;
-  int64_t qrow0 = 0, krow0 = 0;
-  if (p.cu_q) {
-    qrow0 = p.cu_q[b]; Lq = p.cu_q[b + 1] - p.cu_q[b];
-    krow0 = p.cu_k[b]; Lk = p.cu_k[b + 1] - p.cu_k[b];
-  }
+  int Lq, Lk;
+  int64_t qrow0, krow0;
+  seq_bounds(p, b, Lq, Lk, qrow0, krow0);
   int Lkey = kPooled ? p.Lkp : Lk;
   int k0 = kblk * kBlk;
-  // multi-level: level e (p = 2^e) of this work item, its pyramid region start and row count;
-  // pooled items number the level-2, then level-4, then level-8 pyramid blocks
+  // multi-level: level e (p = 2^e) of this work item, its pyramid region start and row count
   int ml_row0 = 0;
-  if (!(kML && kPooled && VB_ML_LONG_FIRST)) ml_m = kblk;
+  if (!(kML && kPooled)) ml_m = kblk;
   if (kML) {
     const MlGeom gm(p.Lpad);
-    if (kPooled && !VB_ML_LONG_FIRST) {
-      ml_e = 1;
-      auto nit = [&](int e) { return ((p.Lpad >> e) + kRows - 1) / kRows; };
-      while (ml_e < 3 && ml_m >= nit(ml_e)) { ml_m -= nit(ml_e); ++ml_e; }
-    }
     ml_row0 = gm.off[ml_e];
     Lkey = kPooled ? p.Lpad >> ml_e : Lk;
     k0 = ml_m * (kPooled ? kRows : kBlk);
@@ -364,7 +310,7 @@ __global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd
 
   const int trr = tr_row(lane), trc = tr_col(lane);
   constexpr int fL = (kPooled && !kML) ? 2 : 0;  // stats fields of this branch
-  constexpr bool kSeed = D == 64 || VB_BWD_SEED128;
+  constexpr bool kSeed = D == 64;   // D=128: dP seeded with -Delta too measured 6 % slower on Wan's dK/dV
 
   if (ntiles > 0) issue(0, 0);
   if (kBufs == 3 && ntiles > 1) issue(1, 1);
@@ -618,20 +564,8 @@ __global__ void __launch_bounds__(kW * 64, D == 128 ? 1 : VB_DKDV_WAVES_D64) bwd
 // ------------------------------------------------------------------------------------------------
 // dQ: one workgroup per (b, h, 128-row q-block); kept full-resolution tiles then pooled tiles
 // ------------------------------------------------------------------------------------------------
-#ifndef VB_DQ_WAVES_D128
-#define VB_DQ_WAVES_D128 2   // D=128: two waves per SIMD with a 2-slot ring (1: one wave, 3-slot ring; Wan backward 1.014-1.018x)
-#endif
-#ifndef VB_DQ_PRIO64
-#define VB_DQ_PRIO64 0     // measured (cog backward): 1 0.990x, 3 0.990x
-#endif
-#ifndef VB_DQ_PRIO128
-#define VB_DQ_PRIO128 1   // measured (Wan backward, two waves per SIMD): 1 1.096x, 3 1.094x
-#endif
-#ifndef VB_DQ_WAVES_D64
-#define VB_DQ_WAVES_D64 2   // waves per SIMD the D=64 dQ kernel is register-budgeted for
-#endif
 template <int D, class T, bool kPool, bool kML = false>
-__global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : VB_DQ_WAVES_D64) bwd_dq_kernel(const BwdParams p) {
+__global__ void __launch_bounds__(bwd::kThreads, D == 128 ? bwd::kDqWavesD128 : bwd::kDqWavesD64) bwd_dq_kernel(const BwdParams p) {
   using namespace bwd;
   constexpr int KS = D / 16;
   constexpr int DT = D / 32;
@@ -642,11 +576,8 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
   constexpr int kCh = RB / 16;
   constexpr int kInst = 2 * kInstTile;
   constexpr int kBufBytes = 2 * kTileBytes;
-  // 2-slot K/V ring with a second barrier per tile: D=64, and D=128 at the default two waves per
-  // SIMD (VB_DQ_WAVES_D128=2, 68 KiB). Only the one-wave D=128 build (VB_DQ_WAVES_D128=1) takes a
-  // 3-slot ring, where tile t is read while t+1 and t+2 are in flight and one barrier per tile both
-  // publishes tile t and proves slot (t-1) % 3 free for tile t+2.
-  constexpr int kRing = (D == 128 && VB_DQ_WAVES_D128 < 2) ? 3 : 2;
+  // 2-slot K/V ring with a second barrier per tile (D=128 at two waves per SIMD: 68 KiB)
+  constexpr int kRing = 2;
   __shared__ __attribute__((aligned(16))) uint8_t smem[kRing * kBufBytes + kMaxBlocks * 2 + 16];
   uint16_t* list = reinterpret_cast<uint16_t*>(smem + kRing * kBufBytes);
   int* list_n = reinterpret_cast<int*>(smem + kRing * kBufBytes + kMaxBlocks * 2);
@@ -656,27 +587,13 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
   const int half = lane >> 5;
   const int l32 = lane & 31;
 
-  // heavy-first, then XCD-contiguous head-major (as the forward)
   const int BH = p.B * p.H;
-  const int hr = min(p.heavy_rows, p.nbq);
-  const int n_heavy = hr * BH;
   int qblk, bh;
-  if ((int)blockIdx.x < n_heavy) {
-    qblk = p.nbq - 1 - (int)(blockIdx.x / BH);
-    bh = blockIdx.x % BH;
-  } else {
-    const int rows_left = p.nbq - hr;
-    const int lin = xcd_linear(blockIdx.x - n_heavy, rows_left * BH);
-    bh = lin / rows_left;
-    qblk = rows_left - 1 - lin % rows_left;
-  }
+  dq_item(p, BH, bh, qblk);
   const int b = bh / p.H, h = bh % p.H;
-  int Lq = p.Lq, Lk = p.Lk;
-  int64_t qrow0 = 0, krow0 = 0;
-  if (p.cu_q) {
-    qrow0 = p.cu_q[b]; Lq = p.cu_q[b + 1] - p.cu_q[b];
-    krow0 = p.cu_k[b]; Lk = p.cu_k[b + 1] - p.cu_k[b];
-  }
+  int Lq, Lk;
+  int64_t qrow0, krow0;
+  seq_bounds(p, b, Lq, Lk, qrow0, krow0);
   const int q0 = qblk * kBlk;
   if (q0 >= Lq) return;
   const int nbk = (Lk + kBlk - 1) / kBlk;
@@ -879,9 +796,8 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
   constexpr int kHi = (kInst + 3) / 4, kLo = kInst / 4;  // DMA instructions per wave and tile
   const bool many = wave < (kInst & 3);
 
-  constexpr bool kSeedQ = D == 64 || VB_BWD_SEED128;
-  // s_setprio 1 around the MFMA chains (bit 0: S and dP, bit 1: the dQ steps) at D=128
-  constexpr int kPrioQ = D == 128 ? VB_DQ_PRIO128 : VB_DQ_PRIO64;
+  constexpr bool kSeedQ = D == 64;
+  constexpr int kPrioQ = D == 128 ? kDqPrio128 : kDqPrio64;
   f32x16 cD, zero;
 #pragma unroll
   for (int r = 0; r < 16; ++r) cD[r] = zero[r] = 0.f;
@@ -889,11 +805,10 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
   if (ntiles > 0) issue(0, I0{});
-  if (kRing == 3 && ntiles > 1) issue(1, I1{});
   // The body is instantiated once per ring slot, so every LDS address is an immediate offset.
   auto body = [&](int t, auto U) __attribute__((always_inline)) {
     constexpr int u_slot = decltype(U)::value;
-    if (kRing == 2 && t + 1 < ntiles) issue(t + 1, std::integral_constant<int, (u_slot + 1) % kRing>{});
+    if (t + 1 < ntiles) issue(t + 1, std::integral_constant<int, (u_slot + 1) % kRing>{});
     // retire this wave's part of tile t (tile t+1's stays in flight), then the barrier
     if (t + 1 < ntiles) {
       if (many) VB_WAIT_VMCNT(kHi);
@@ -902,7 +817,6 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
       VB_WAIT_VMCNT(0);
     }
     __builtin_amdgcn_s_barrier();
-    if (kRing == 3 && t + 2 < ntiles) issue(t + 2, std::integral_constant<int, (u_slot + 2) % kRing>{});
     int kstart, klen;
     float nL;
     bool pooled;
@@ -986,13 +900,11 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? VB_DQ_WAVES_D128 : V
       }
       if constexpr (kPrioQ & 2) __builtin_amdgcn_s_setprio(0);
     }
-    if (kRing == 2) __builtin_amdgcn_s_barrier();   // slot t % 2 is refilled by the next issue
+    __builtin_amdgcn_s_barrier();   // slot t % 2 is refilled by the next issue
   };
   for (int t0 = 0; t0 < ntiles; t0 += kRing) {
     body(t0, I0{});
     if (t0 + 1 < ntiles) body(t0 + 1, I1{});
-    if constexpr (kRing > 2)
-      if (t0 + 2 < ntiles) body(t0 + 2, std::integral_constant<int, 2>{});
   }
 
   if (!qvalid) return;
@@ -1027,489 +939,61 @@ __global__ void __launch_bounds__(256) pool_grad_reduce_kernel(const float* pk, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side
+// launchers (vb_attn_bwd.hpp); the host layer is vb_attn_bwd_host.cpp
 // ------------------------------------------------------------------------------------------------
-#ifndef VB_BWD_FORK
-#define VB_BWD_FORK 1   // D=128: dQ on a side stream beside the dK/dV chain (they share only the prep's output)
-#endif
-// dQ depends only on the prep kernel's row statistics; the dK/dV chain (pooled keys, their reduce,
-// main keys) never reads dQ. So dQ is launched on a per-device side stream that waits for the
-// caller's stream at the fork and is joined back (an event) before the call returns: the two
-// launches fill each other's last rounds and the chain's small launches. Work and results are
-// unchanged (no atomics, disjoint outputs). Graph capture: the side stream joins the caller's
-// capture through the event wait. The mutex keeps one call's record/wait pairs together.
-// Measured (tools/ab.py, profiles/r06_bwd_fork_ab.log): Wan backward 1.016-1.019x, CogVideoX
-// 0.998-1.000x, the multi-level backward 0.987-0.990x, so only the D=128 main backward forks.
-struct BwdFork {
-  hipStream_t side = nullptr;
-  hipEvent_t forked = nullptr, joined = nullptr;
-};
-class ForkScope {
- public:
-  ForkScope(hipStream_t s, bool enable) : s_(s), lock_(mu(), std::defer_lock) {
-    if (!VB_BWD_FORK || !enable) return;
-    lock_.lock();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    BwdFork& f = forks()[dev];
-    if (!f.side) {
-      if (hipStreamCreateWithFlags(&f.side, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&f.forked, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&f.joined, hipEventDisableTiming) != hipSuccess) {
-        f = BwdFork{};
-        return;   // no side stream: everything stays on the caller's stream
-      }
-    }
-    if (hipEventRecord(f.forked, s) != hipSuccess || hipStreamWaitEvent(f.side, f.forked, 0) != hipSuccess) return;
-    f_ = &f;
-  }
-  ~ForkScope() {
-    if (f_ && hipEventRecord(f_->joined, f_->side) == hipSuccess) (void)hipStreamWaitEvent(s_, f_->joined, 0);
-  }
-  hipStream_t dq_stream() const { return f_ ? f_->side : s_; }
-  bool forked() const { return f_ != nullptr; }
-
- private:
-  static std::mutex& mu() {
-    static std::mutex m;
-    return m;
-  }
-  static std::map<int, BwdFork>& forks() {
-    static std::map<int, BwdFork> m;
-    return m;
-  }
-  hipStream_t s_;
-  std::unique_lock<std::mutex> lock_;   // held from the fork to the join (the destructor's event wait)
-  BwdFork* f_ = nullptr;
-};
-
-template <class T>
-static int launch_prep(const PrepParams& pp, hipStream_t s) {
+int launch_prep(const PrepParams& pp, int dtype, hipStream_t s) {
   const int64_t threads = (int64_t)pp.B * pp.H * pp.ntile * 64 * (pp.D / 8);
   const dim3 grid((unsigned)((threads + 255) / 256));
-  hipLaunchKernelGGL(bwd_prep_kernel<T>, grid, dim3(256), 0, s, pp);
+  if (dtype == VB_DTYPE_BF16) hipLaunchKernelGGL(bwd_prep_kernel<BF16>, grid, dim3(256), 0, s, pp);
+  else hipLaunchKernelGGL(bwd_prep_kernel<F16>, grid, dim3(256), 0, s, pp);
   return check_launch("bwd_prep_kernel");
 }
 
-// kernel choice: vb_attn_bwd_args.kernel_select (VB_BWD_SEL_* bits); `ran` collects VB_BWD_RAN_* bits
-template <int D, class T>
-static int launch_dq(const BwdParams& p, bool pool, hipStream_t s, int sel, int& ran) {
-  constexpr bool kF16 = std::is_same<T, F16>::value;
-  if (!(sel & VB_BWD_SEL_DQ_ROUND3)) return launch_dq_pipe(p, D, pool, kF16, s, sel, ran);
-  ran |= VB_BWD_RAN_DQ_ROUND3;
+int launch_dkdv_round3(const BwdParams& p, int D, int dtype, bool pooled, hipStream_t s) {
   const int BH = p.B * p.H;
-  if (pool)
-    hipLaunchKernelGGL((bwd_dq_kernel<D, T, true>), dim3(p.nbq * BH), dim3(bwd::kThreads), 0, s, p);
-  else
-    hipLaunchKernelGGL((bwd_dq_kernel<D, T, false>), dim3(p.nbq * BH), dim3(bwd::kThreads), 0, s, p);
-  return check_launch("bwd_dq_kernel");
+  const dim3 grid(pooled ? p.nbkp * BH * p.psplit : p.nbk * BH);
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto pl) {
+    hipLaunchKernelGGL((bwd_dkdv_kernel<d(), decltype(t), pl()>), grid, dim3(bwd::kThreads), 0, s, p);
+    return check_launch(pl() ? "bwd_dkdv_kernel<pooled>" : "bwd_dkdv_kernel");
+  }, pooled);
 }
 
-template <int D, class T>
-static int launch_grads(const BwdParams& p, bool pool, hipStream_t s, int sel, int& ran) {
-  const int BH = p.B * p.H;
-  const bool pipe = !(sel & VB_BWD_SEL_DKDV_ROUND3);
-  if ((pool && p.dkp) || p.k) ran |= pipe ? VB_BWD_RAN_DKDV_PIPE : VB_BWD_RAN_DKDV_ROUND3;
-  constexpr bool kF16 = std::is_same<T, F16>::value;
-  ForkScope fork(s, D == 128);
-  if (fork.forked())   // dQ first, on the side stream
-    if (int rc = launch_dq<D, T>(p, pool, fork.dq_stream(), sel, ran)) return rc;
-  if (pool && p.dkp) {
-    if (pipe) {
-      if (int rc = launch_dkdv_pipe(p, D, true, kF16, s)) return rc;
-    } else {
-      hipLaunchKernelGGL((bwd_dkdv_kernel<D, T, true>), dim3(p.nbkp * BH * p.psplit), dim3(bwd::kThreads), 0, s, p);
-      if (int rc = check_launch("bwd_dkdv_kernel<pooled>")) return rc;
-    }
-    if (p.psplit > 1) {
-      const int64_t n4 = (int64_t)BH * p.Lkp * D / 4;
-      hipLaunchKernelGGL(pool_grad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dkp_part,
-                         p.dvp_part, n4, p.psplit, p.dkp, p.dvp);
-      if (int rc = check_launch("pool_grad_reduce_kernel")) return rc;
-    }
-  }
-  if (p.k) {
-    if (pipe) {
-      if (int rc = launch_dkdv_pipe(p, D, false, kF16, s)) return rc;
-    } else {
-      hipLaunchKernelGGL((bwd_dkdv_kernel<D, T, false>), dim3(p.nbk * BH), dim3(bwd::kThreads), 0, s, p);
-      if (int rc = check_launch("bwd_dkdv_kernel")) return rc;
-    }
-  }
-  return fork.forked() ? 0 : launch_dq<D, T>(p, pool, s, sel, ran);
+int launch_ml_dkdv_round3(const BwdParams& p, int D, int dtype, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t) {
+    hipLaunchKernelGGL((bwd_dkdv_kernel<d(), decltype(t), false, true>), dim3(p.nbk * p.B * p.H), dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dkdv_kernel<multi-level>");
+  });
 }
 
-static int dispatch_bwd(const PrepParams& pp, const BwdParams& p, int D, int dtype, bool pool, hipStream_t s,
-                        int sel = 0, int32_t* ran_out = nullptr) {
-  int ran = 0, rc;
-  if (dtype == VB_DTYPE_BF16) {
-    rc = launch_prep<BF16>(pp, s);
-    if (!rc) rc = D == 64 ? launch_grads<64, BF16>(p, pool, s, sel, ran) : launch_grads<128, BF16>(p, pool, s, sel, ran);
-  } else {
-    rc = launch_prep<F16>(pp, s);
-    if (!rc) rc = D == 64 ? launch_grads<64, F16>(p, pool, s, sel, ran) : launch_grads<128, F16>(p, pool, s, sel, ran);
-  }
-  if (ran_out) *ran_out = ran;
-  return rc;
+int launch_dq_round3(const BwdParams& p, int D, int dtype, bool pool, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto pl) {
+    hipLaunchKernelGGL((bwd_dq_kernel<d(), decltype(t), pl()>), dim3(p.nbq * p.B * p.H), dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dq_kernel");
+  }, pool);
 }
 
-struct WsLayout {
-  uint64_t stats, q_r, do_r, dkp, dvp, dkp_part, dvp_part, total;
-  int psplit;
-};
-// pooled-key q-range split: aim at ~3k workgroups per sample for the pooled dK/dV pass. The split
-// sets the order of the partial sums, so it does not depend on B: a sample's gradients are the
-// same bits in any batch (the B=5 training-batch test).
-static int pool_split(int B, int H, int Lq, int Lkp) {
-  (void)B;
-  if (Lkp <= 0) return 1;
-  const int nbkp = (Lkp + 127) / 128, nbq = (Lq + 127) / 128;
-  const int wg = nbkp * H;
-  int s = (3072 + wg / 2) / wg;
-  return s < 1 ? 1 : (s > nbq ? nbq : s);
-}
-static WsLayout ws_layout(int B, int H, int Lq, int D, bool copies, int Lkp) {
-  auto up = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-  WsLayout w{};
-  const uint64_t ntile = (uint64_t)((Lq + 63) / 64);
-  uint64_t off = 0;
-  w.stats = off; off = up(off + (uint64_t)B * H * ntile * 256 * 4);
-  w.q_r = w.do_r = 0;
-  if (copies) {
-    w.q_r = off; off = up(off + (uint64_t)B * H * Lq * D * 2);
-    w.do_r = off; off = up(off + (uint64_t)B * H * Lq * D * 2);
-  }
-  w.dkp = w.dvp = w.dkp_part = w.dvp_part = 0;
-  w.psplit = pool_split(B, H, Lq, Lkp);
-  if (Lkp > 0) {
-    w.dkp = off; off = up(off + (uint64_t)B * H * Lkp * D * 4);
-    w.dvp = off; off = up(off + (uint64_t)B * H * Lkp * D * 4);
-    w.dkp_part = w.dkp; w.dvp_part = w.dvp;
-    if (w.psplit > 1) {
-      w.dkp_part = off; off = up(off + (uint64_t)w.psplit * B * H * Lkp * D * 4);
-      w.dvp_part = off; off = up(off + (uint64_t)w.psplit * B * H * Lkp * D * 4);
-    }
-  }
-  w.total = off;
-  return w;
+int launch_ml_dq_round3(const BwdParams& p, int D, int dtype, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t) {
+    hipLaunchKernelGGL((bwd_dq_kernel<d(), decltype(t), false, true>), dim3(p.nbq * p.B * p.H), dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dq_kernel<multi-level>");
+  });
 }
 
-static bool mul8(const int64_t* s) { return ((s[0] | s[1] | s[2]) & 7) == 0; }
-// one (b,h) slice of L rows at `row_stride` elements must be addressable by a 32-bit buffer offset
-static bool slice_ok(int L, int64_t row_stride, int D) {
-  return (int64_t)(L - 1) * 2 * row_stride + 2 * D < (int64_t(1) << 31);
-}
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace vb
-
-extern "C" uint64_t vb_attn_bwd_workspace_size(const vb_attn_bwd_args* a) {
-  if (!a) return 0;
-  return vb::ws_layout(a->B, a->H, a->Lq, a->D, a->q_rows != nullptr, a->kp ? a->Lkp : 0).total;
+int launch_pool_grad_reduce(const BwdParams& p, int D, hipStream_t s) {
+  const int64_t n4 = (int64_t)p.B * p.H * p.Lkp * D / 4;
+  hipLaunchKernelGGL(pool_grad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, p.dkp_part,
+                     p.dvp_part, n4, p.psplit, p.dkp, p.dvp);
+  return check_launch("pool_grad_reduce_kernel");
 }
 
-extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
-  using namespace vb;
-  if (!a) return fail(VB_ERR_INVALID, "vb_attn_bwd: null args");
-  if (a->B <= 0 || a->H <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->D <= 0)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: B, H, Lq, Lk, D must be positive");
-  if (a->D != 64 && a->D != 128)
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: head_dim must be 64 or 128, got " + std::to_string(a->D));
-  if (a->dtype != VB_DTYPE_BF16 && a->dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, "vb_attn_bwd: unknown dtype");
-  if (!a->q || !a->k || !a->v || !a->out || !a->lse || !a->dout || !a->dq || !a->dk || !a->dv)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: missing tensor");
-  if (a->kernel_select & ~(VB_BWD_SEL_DKDV_ROUND3 | VB_BWD_SEL_DQ_ROUND3 | VB_BWD_SEL_DQ_RING4))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: unknown kernel_select bits");
-  const bool pool = a->kp != nullptr;
-  if (pool && (!a->vp || a->Lkp <= 0 || !a->out2 || !a->lse2 || a->pool_gap <= 0))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: pooled branch needs vp, Lkp, out2, lse2 and pool_gap");
-  if (pool && (int64_t)a->Lkp * a->pool_gap < a->Lk)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: Lkp * pool_gap must cover Lk");
-  const int nbk = (a->Lk + 127) / 128;
-  const int nbq = (a->Lq + 127) / 128;
-  if (nbk > bwd::kMaxBlocks || nbq > bwd::kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: sequence too long");
-  const int64_t* strides[] = {a->q_stride, a->k_stride, a->v_stride, a->out_stride, a->dout_stride,
-                              a->dq_stride, a->dk_stride, a->dv_stride};
-  for (const int64_t* s : strides)
-    if (!mul8(s)) return fail(VB_ERR_INVALID, "vb_attn_bwd: strides must be multiples of 8 elements");
-  if (pool && (!mul8(a->kp_stride) || !mul8(a->vp_stride) || !mul8(a->out2_stride)))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: strides must be multiples of 8 elements");
-  const void* ptrs[] = {a->q, a->k, a->v, a->out, a->dout, a->dq, a->dk, a->dv};
-  for (const void* q : ptrs)
-    if (!al16(q)) return fail(VB_ERR_INVALID, "vb_attn_bwd: tensors must be 16-byte aligned");
-  if (pool && (!al16(a->kp) || !al16(a->vp) || !al16(a->out2)))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: tensors must be 16-byte aligned");
-  const WsLayout w = ws_layout(a->B, a->H, a->Lq, a->D, a->q_rows != nullptr, pool ? a->Lkp : 0);
-  if (!a->workspace || a->workspace_bytes < w.total || !al16(a->workspace))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: workspace missing or smaller than vb_attn_bwd_workspace_size()");
-  if (!a->q_rows && (!slice_ok(a->Lq, a->q_stride[2], a->D) || !slice_ok(a->Lq, a->dout_stride[2], a->D)))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: a q/dout (b,h) slice spans >= 2 GiB");
-  if (!slice_ok(a->Lk, a->k_stride[2], a->D) || !slice_ok(a->Lk, a->v_stride[2], a->D) ||
-      (pool && (!slice_ok(a->Lkp, a->kp_stride[2], a->D) || !slice_ok(a->Lkp, a->vp_stride[2], a->D))))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: a k/v/kp/vp (b,h) slice spans >= 2 GiB");
-  uint8_t* ws = reinterpret_cast<uint8_t*>(a->workspace);
-
-  PrepParams pp{};
-  pp.q = a->q; pp.dout = a->dout; pp.out = a->out; pp.out2 = pool ? a->out2 : nullptr;
-  for (int i = 0; i < 3; ++i) {
-    pp.qs[i] = a->q_stride[i]; pp.dos[i] = a->dout_stride[i]; pp.os[i] = a->out_stride[i];
-    pp.o2s[i] = pool ? a->out2_stride[i] : 0;
-  }
-  pp.lse = a->lse; pp.lse2 = pool ? a->lse2 : nullptr; pp.alpha = a->alpha;
-  pp.q_rows = a->q_rows;
-  pp.stats = reinterpret_cast<float*>(ws + w.stats);
-  if (a->q_rows) { pp.q_r = ws + w.q_r; pp.do_r = ws + w.do_r; }
-  pp.B = a->B; pp.H = a->H; pp.Lq = a->Lq; pp.D = a->D; pp.ntile = (a->Lq + 63) / 64;
-
-  BwdParams p{};
-  if (a->q_rows) {
-    p.q = ws + w.q_r; p.dout = ws + w.do_r;
-    p.qs[0] = p.dos[0] = (int64_t)a->H * a->Lq * a->D;
-    p.qs[1] = p.dos[1] = (int64_t)a->Lq * a->D;
-    p.qs[2] = p.dos[2] = a->D;
-  } else {
-    p.q = a->q; p.dout = a->dout;
-    for (int i = 0; i < 3; ++i) { p.qs[i] = a->q_stride[i]; p.dos[i] = a->dout_stride[i]; }
-  }
-  p.k = a->k; p.v = a->v;
-  for (int i = 0; i < 3; ++i) {
-    p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i];
-    p.ms[i] = a->mask_stride[i];
-    p.dqs[i] = a->dq_stride[i]; p.dks[i] = a->dk_stride[i]; p.dvs[i] = a->dv_stride[i];
-    if (pool) { p.kps[i] = a->kp_stride[i]; p.vps[i] = a->vp_stride[i]; }
-  }
-  p.kp = pool ? a->kp : nullptr; p.vp = pool ? a->vp : nullptr; p.Lkp = pool ? a->Lkp : 0;
-  p.mask = a->block_mask;
-  p.stats = pp.stats; p.ntile = pp.ntile;
-  p.dq = a->dq; p.q_rows = a->q_rows;
-  p.dk = a->dk; p.dv = a->dv; p.kv_rows = a->kv_rows;
-  p.psplit = 1;
-  if (pool) {
-    p.dkp = reinterpret_cast<float*>(ws + w.dkp); p.dvp = reinterpret_cast<float*>(ws + w.dvp);
-    p.psplit = w.psplit;
-    p.dkp_part = reinterpret_cast<float*>(ws + w.dkp_part); p.dvp_part = reinterpret_cast<float*>(ws + w.dvp_part);
-  }
-  p.gap = pool ? a->pool_gap : 1;
-  p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.nbq = nbq; p.nbk = nbk;
-  p.nbkp = pool ? (a->Lkp + 127) / 128 : 0;
-  p.scale = a->scale > 0.f ? a->scale : (float)(1.0 / sqrt((double)a->D));
-  p.c = p.scale * kLog2e;
-  p.heavy_rows = a->heavy_rows;
-  return dispatch_bwd(pp, p, a->D, a->dtype, pool, reinterpret_cast<hipStream_t>(stream), a->kernel_select,
-                      a->kernels_ran);
-}
-
-extern "C" uint64_t vb_block_sparse_attn_bwd_workspace_size(int batch, int num_heads, int max_seqlen_q) {
-  if (batch <= 0 || num_heads <= 0 || max_seqlen_q <= 0) return 0;
-  return vb::ws_layout(batch, num_heads, max_seqlen_q, 64, false, 0).total;
-}
-
-extern "C" int vb_block_sparse_attn_bwd(const void* dout, const void* q_unpad, const void* k_unpad,
-                                        const void* v_unpad, const void* out_unpad, const float* softmax_lse,
-                                        const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
-                                        const int32_t* head_mask_type, const int32_t* streaming_info,
-                                        const uint8_t* base_blockmask, int batch, int num_heads, int head_dim,
-                                        int max_seqlen_q, int max_seqlen_k, float p_dropout, float softmax_scale,
-                                        int is_causal, int exact_streaming, int deterministic, int dtype,
-                                        void* dq, void* dk, void* dv, void* workspace, uint64_t workspace_bytes,
-                                        int mask_head_mode, void* stream) {
-  using namespace vb;
-  (void)streaming_info;
-  (void)deterministic;  // always deterministic (no atomics)
-  if (p_dropout != 0.f) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: p_dropout must be 0");
-  if (is_causal || exact_streaming) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: causal/streaming not supported");
-  if (mask_head_mode != VB_MASK_HEAD_PER_HEAD && mask_head_mode != VB_MASK_HEAD_SHARED0)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: unknown mask_head_mode");
-  if (!dout || !q_unpad || !k_unpad || !v_unpad || !out_unpad || !softmax_lse || !cu_seqlens_q || !cu_seqlens_k ||
-      !dq || !dk || !dv)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: null tensor");
-  if (batch <= 0 || num_heads <= 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: bad sizes");
-  if (head_dim != 64 && head_dim != 128)
-    return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: head_dim must be 64 or 128");
-  if (dtype != VB_DTYPE_BF16 && dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: unknown dtype");
-  const int nbq = (max_seqlen_q + 127) / 128;
-  const int nbk = (max_seqlen_k + 127) / 128;
-  if (nbk > bwd::kMaxBlocks || nbq > bwd::kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: sequence too long");
-  const WsLayout w = ws_layout(batch, num_heads, max_seqlen_q, head_dim, false, 0);
-  if (!workspace || workspace_bytes < w.total || !al16(workspace))
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: workspace missing or too small");
-  if (!slice_ok(max_seqlen_q, (int64_t)num_heads * head_dim, head_dim))
-    return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: a sequence's q/dout span >= 2 GiB");
-  if (!slice_ok(max_seqlen_k, (int64_t)num_heads * head_dim, head_dim))
-    return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_bwd: a sequence's k/v span >= 2 GiB");
-  const void* ptrs[] = {dout, q_unpad, k_unpad, v_unpad, out_unpad, dq, dk, dv};
-  for (const void* q : ptrs)
-    if (!al16(q)) return fail(VB_ERR_INVALID, "vb_block_sparse_attn_bwd: tensors must be 16-byte aligned");
-  const int64_t row = (int64_t)num_heads * head_dim;
-  int64_t s3[3] = {0, head_dim, row};
-
-  PrepParams pp{};
-  pp.q = q_unpad; pp.dout = dout; pp.out = out_unpad;
-  for (int i = 0; i < 3; ++i) pp.qs[i] = pp.dos[i] = pp.os[i] = s3[i];
-  pp.lse = softmax_lse;
-  pp.cu_q = cu_seqlens_q;
-  pp.stats = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(workspace) + w.stats);
-  pp.B = batch; pp.H = num_heads; pp.Lq = max_seqlen_q; pp.D = head_dim; pp.ntile = (max_seqlen_q + 63) / 64;
-
-  BwdParams p{};
-  p.q = q_unpad; p.dout = dout; p.k = k_unpad; p.v = v_unpad;
-  for (int i = 0; i < 3; ++i) p.qs[i] = p.dos[i] = p.ks[i] = p.vs[i] = p.dqs[i] = p.dks[i] = p.dvs[i] = s3[i];
-  p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k; p.head_mask_type = head_mask_type;
-  p.hm_mode = mask_head_mode;
-  p.mask = base_blockmask;
-  p.ms[0] = head_mask_type ? -1 : (int64_t)num_heads * nbq * nbk;
-  p.ms[1] = (int64_t)nbq * nbk; p.ms[2] = nbk;
-  p.stats = pp.stats; p.ntile = pp.ntile;
-  p.dq = dq; p.dk = dk; p.dv = dv;
-  p.gap = 1;
-  p.psplit = 1;
-  p.B = batch; p.H = num_heads; p.Lq = max_seqlen_q; p.Lk = max_seqlen_k; p.nbq = nbq; p.nbk = nbk;
-  p.scale = softmax_scale > 0.f ? softmax_scale : (float)(1.0 / sqrt((double)head_dim));
-  p.c = p.scale * kLog2e;
-  return dispatch_bwd(pp, p, head_dim, dtype, false, reinterpret_cast<hipStream_t>(stream));
-}
-
-// ------------------------------------------------------------------------------------------------
-// multi-level backward (kernels/block_sparse_attn_kernel_with_backward_9_10.py _backward :1375-1576)
-// ------------------------------------------------------------------------------------------------
-namespace vb {
-struct MlWs {
-  uint64_t stats, q_r, do_r, dkpyr, dvpyr, total;
-};
-static MlWs ml_ws_layout(int B, int H, int L, int D, bool copies) {
-  auto up = [](uint64_t x) { return (x + 255) & ~uint64_t(255); };
-  MlWs w{};
-  const uint64_t ntile = (uint64_t)((L + 63) / 64);
-  const uint64_t lpad = (uint64_t)(L + 127) / 128 * 128;
-  uint64_t off = 0;
-  w.stats = off; off = up(off + (uint64_t)B * H * ntile * 256 * 4);
-  if (copies) {
-    w.q_r = off; off = up(off + (uint64_t)B * H * L * D * 2);
-    w.do_r = off; off = up(off + (uint64_t)B * H * L * D * 2);
-  }
-  w.dkpyr = off; off = up(off + (uint64_t)B * H * (7 * lpad / 8) * D * 4);
-  w.dvpyr = off; off = up(off + (uint64_t)B * H * (7 * lpad / 8) * D * 4);
-  w.total = off;
-  return w;
-}
-
-template <int D, class T>
-static int launch_ml_grads(const PrepParams& pp, const BwdParams& p, hipStream_t s, int sel, int& ran) {
-  if (int rc = launch_prep<T>(pp, s)) return rc;
-  ran |= VB_BWD_RAN_ML_PYRAMID;
-  const int BH = p.B * p.H;
-  // dQ stays last on the caller's stream: forked beside the pyramid and level-1 passes it measured
-  // 0.987-0.990x (ForkScope)
-  {
-    constexpr int kW = D == 64 ? VB_ML_PYR_WAVES : 4, kRows = 32 * kW;   // items of kRows pyramid rows
+int launch_ml_pyramid(const BwdParams& p, int D, int dtype, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t) {
+    constexpr int kW = d() == 64 ? bwd::kMlPyrWaves : 4, kRows = 32 * kW;   // items of kRows pyramid rows
     int items = 0;
     for (int e = 1; e < 4; ++e) items += ((p.Lpad >> e) + kRows - 1) / kRows;
-    hipLaunchKernelGGL((bwd_dkdv_kernel<D, T, true, true, kW>), dim3(items * BH), dim3(kW * 64), 0, s, p);
-  }
-  if (int rc = check_launch("bwd_dkdv_kernel<multi-level pooled>")) return rc;
-  if (!(sel & VB_BWD_SEL_DKDV_ROUND3)) {
-    ran |= VB_BWD_RAN_DKDV_PIPE;
-    if (int rc = launch_ml_dkdv_pipe(p, D, std::is_same<T, F16>::value, s)) return rc;
-  } else {
-    ran |= VB_BWD_RAN_DKDV_ROUND3;
-    hipLaunchKernelGGL((bwd_dkdv_kernel<D, T, false, true>), dim3(p.nbk * BH), dim3(bwd::kThreads), 0, s, p);
-    if (int rc = check_launch("bwd_dkdv_kernel<multi-level>")) return rc;
-  }
-  if (!(sel & VB_BWD_SEL_DQ_ROUND3)) {
-    ran |= VB_BWD_RAN_DQ_PIPE_RING2;
-    return launch_ml_dq_pipe(p, D, std::is_same<T, F16>::value, s);
-  }
-  ran |= VB_BWD_RAN_DQ_ROUND3;
-  hipLaunchKernelGGL((bwd_dq_kernel<D, T, false, true>), dim3(p.nbq * BH), dim3(bwd::kThreads), 0, s, p);
-  return check_launch("bwd_dq_kernel<multi-level>");
+    hipLaunchKernelGGL((bwd_dkdv_kernel<d(), decltype(t), true, true, kW>), dim3(items * p.B * p.H), dim3(kW * 64), 0, s, p);
+    return check_launch("bwd_dkdv_kernel<multi-level pooled>");
+  });
 }
+
 }  // namespace vb
-
-extern "C" uint64_t vb_ml_attn_bwd_workspace_size(const vb_ml_attn_bwd_args* a) {
-  if (!a || a->B <= 0 || a->H <= 0 || a->L <= 0 || a->D <= 0) return 0;
-  return vb::ml_ws_layout(a->B, a->H, a->L, a->D, a->rows != nullptr).total;
-}
-
-extern "C" int vb_ml_attn_bwd(const vb_ml_attn_bwd_args* a, void* stream) {
-  using namespace vb;
-  if (!a) return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: null args");
-  if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: B, H, L must be positive");
-  if (a->D != 64 && a->D != 128)
-    return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_bwd: head_dim must be 64 or 128, got " + std::to_string(a->D));
-  if (a->dtype != VB_DTYPE_BF16 && a->dtype != VB_DTYPE_F16) return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: unknown dtype");
-  if (!a->q || !a->kpyr || !a->vpyr || !a->level_mask || !a->out || !a->lse || !a->dout || !a->dq || !a->dk || !a->dv)
-    return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: missing tensor");
-  if (a->kernel_select & ~(VB_BWD_SEL_DKDV_ROUND3 | VB_BWD_SEL_DQ_ROUND3))
-    return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: unsupported kernel_select bits (the multi-level dQ has one ring)");
-  const int nb = (a->L + 127) / 128;
-  if (nb > bwd::kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_bwd: sequence too long");
-  const int64_t* strides[] = {a->q_stride, a->out_stride, a->dout_stride, a->dq_stride, a->dk_stride, a->dv_stride};
-  for (const int64_t* st : strides)
-    if (!mul8(st)) return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: strides must be multiples of 8 elements");
-  const void* ptrs[] = {a->q, a->kpyr, a->vpyr, a->out, a->dout, a->dq, a->dk, a->dv};
-  for (const void* q : ptrs)
-    if (!al16(q)) return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: tensors must be 16-byte aligned");
-  const MlWs w = ml_ws_layout(a->B, a->H, a->L, a->D, a->rows != nullptr);
-  if (!a->workspace || a->workspace_bytes < w.total || !al16(a->workspace))
-    return fail(VB_ERR_INVALID, "vb_ml_attn_bwd: workspace missing or smaller than vb_ml_attn_bwd_workspace_size()");
-  if (!a->rows && (!slice_ok(a->L, a->q_stride[2], a->D) || !slice_ok(a->L, a->dout_stride[2], a->D)))
-    return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_bwd: a q/dout (b,h) slice spans >= 2 GiB");
-  if ((int64_t)vb_kv_pyramid_rows(a->L) * 2 * a->D >= (int64_t(1) << 31))
-    return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_bwd: a pyramid (b,h) slice spans >= 2 GiB");
-  uint8_t* ws = reinterpret_cast<uint8_t*>(a->workspace);
-  const int Lpad = nb * 128;
-  const int R = 15 * (Lpad / 8);
-
-  PrepParams pp{};
-  pp.q = a->q; pp.dout = a->dout; pp.out = a->out;
-  for (int i = 0; i < 3; ++i) { pp.qs[i] = a->q_stride[i]; pp.dos[i] = a->dout_stride[i]; pp.os[i] = a->out_stride[i]; }
-  pp.lse = a->lse;
-  pp.q_rows = a->rows;
-  pp.stats = reinterpret_cast<float*>(ws + w.stats);
-  if (a->rows) { pp.q_r = ws + w.q_r; pp.do_r = ws + w.do_r; }
-  pp.B = a->B; pp.H = a->H; pp.Lq = a->L; pp.D = a->D; pp.ntile = (a->L + 63) / 64;
-
-  BwdParams p{};
-  if (a->rows) {
-    p.q = ws + w.q_r; p.dout = ws + w.do_r;
-    p.qs[0] = p.dos[0] = (int64_t)a->H * a->L * a->D;
-    p.qs[1] = p.dos[1] = (int64_t)a->L * a->D;
-    p.qs[2] = p.dos[2] = a->D;
-  } else {
-    p.q = a->q; p.dout = a->dout;
-    for (int i = 0; i < 3; ++i) { p.qs[i] = a->q_stride[i]; p.dos[i] = a->dout_stride[i]; }
-  }
-  p.k = a->kpyr; p.v = a->vpyr;
-  p.ks[0] = p.vs[0] = (int64_t)a->H * R * a->D;
-  p.ks[1] = p.vs[1] = (int64_t)R * a->D;
-  p.ks[2] = p.vs[2] = a->D;
-  for (int i = 0; i < 3; ++i) {
-    p.ms[i] = a->mask_stride[i];
-    p.dqs[i] = a->dq_stride[i]; p.dks[i] = a->dk_stride[i]; p.dvs[i] = a->dv_stride[i];
-  }
-  p.mask = a->level_mask;
-  p.stats = pp.stats; p.ntile = pp.ntile;
-  p.dq = a->dq; p.q_rows = a->rows;
-  p.dk = a->dk; p.dv = a->dv; p.kv_rows = a->rows;
-  p.psplit = 1;
-  p.gap = 1;
-  p.B = a->B; p.H = a->H; p.Lq = a->L; p.Lk = a->L; p.nbq = nb; p.nbk = nb;
-  p.nbkp = (nb + 1) / 2 + (nb + 3) / 4 + (nb + 7) / 8;
-  p.Lpad = Lpad;
-  p.ref_tail = a->ref_tail ? 1 : 0;
-  p.dkpyr = reinterpret_cast<float*>(ws + w.dkpyr);
-  p.dvpyr = reinterpret_cast<float*>(ws + w.dvpyr);
-  p.scale = a->scale > 0.f ? a->scale : (float)(1.0 / sqrt((double)a->D));
-  p.c = p.scale * kLog2e;
-  p.heavy_rows = a->heavy_rows;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int sel = a->kernel_select;
-  int ran = 0, rc;
-  if (a->dtype == VB_DTYPE_BF16)
-    rc = a->D == 64 ? launch_ml_grads<64, BF16>(pp, p, st, sel, ran) : launch_ml_grads<128, BF16>(pp, p, st, sel, ran);
-  else
-    rc = a->D == 64 ? launch_ml_grads<64, F16>(pp, p, st, sel, ran) : launch_ml_grads<128, F16>(pp, p, st, sel, ran);
-  if (a->kernels_ran) *a->kernels_ran = ran;
-  return rc;
-}

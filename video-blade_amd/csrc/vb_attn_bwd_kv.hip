@@ -25,63 +25,13 @@
 #include <type_traits>
 #include <utility>
 
+#include "vb_args.hpp"
 #include "vb_attn_bwd.hpp"
-
-#ifndef VB_KV64_WAVES
-#define VB_KV64_WAVES 1    // waves per SIMD the D=64 kernel is register-budgeted for (2 spills)
-#endif
-#ifndef VB_BWD_DQ128_RING
-// ring slots of the D=128 dQ pipeline: 2 (two workgroups per CU; Wan backward 1.073x over the
-// round-3 dQ, 1.057x over the 4-slot form, profiles/archive/r05_bwd_dq2_ab.log) or 4 (one per CU)
-#define VB_BWD_DQ128_RING 2
-#endif
-#ifndef VB_DQ2_LA
-#define VB_DQ2_LA 2        // operand lookahead of the 2-slot dQ pipeline
-#endif
-#ifndef VB_BWD_DQ64_RING
-// ring slots of the D=64 dQ pipeline: 2 (CogVideoX backward 1.011x over 4, bit-for-bit the same
-// math as the D=128 form; profiles/archive/r05_bwd_dq64_ring_ab.log) or 4
-#define VB_BWD_DQ64_RING 2
-#endif
-#ifndef VB_DQ64_R2_WGS
-#define VB_DQ64_R2_WGS 2     // workgroups per CU the D=64 2-slot form is register-budgeted for (3: 1.005x)
-#endif
-#ifndef VB_KV128_LA
-#define VB_KV128_LA 4      // operand lookahead in MFMAs
-#endif
-#ifndef VB_KV128_NODMA
-#define VB_KV128_NODMA 0   // diagnostic (wrong results): no DMA after the prologue
-#endif
-#ifndef VB_KV_ABL
-#define VB_KV_ABL 0        // diagnostic ablations of the dK/dV kernel (wrong results): bit 0 no score
-                           // VALU, bit 1 no operand LDS reads in the loop, bit 2 no tile barrier,
-                           // bit 4 no DMA after the prologue
-#endif
-// s_nop 1 ahead of the asm MFMAs that read VALU-written registers (the packed P / dS, the -Delta
-// seeds): off by default — the schedule places every such write >= 2 instructions before its MFMA,
-// which tools/diag/mfma_hazard_check.py verifies on the ISA in tests/test_codegen.py (measured
-// 2.2 % on the Wan backward)
-#ifndef VB_KV_YNOP
-#define VB_KV_YNOP 0
-#endif
-#if VB_KV_YNOP
-#define KV_YNOP "s_nop 1\n\t"
-#else
-#define KV_YNOP ""
-#endif
-#ifndef VB_KV128_XNOP
-#define VB_KV128_XNOP 0    // 1: s_nop 1 ahead of the S/dP MFMAs too (measured 2 % slower on the Wan backward)
-#endif
-#if VB_KV128_XNOP
-#define KV_XNOP "s_nop 1\n\t"
-#else
-#define KV_XNOP ""
-#endif
 
 namespace vb {
 namespace kvp {
 
-constexpr int kLA = VB_KV128_LA;
+constexpr int kLA = bwd::kKvLA;
 static_assert(kLA >= 2 && kLA <= 4, "lookahead out of range (the next tile's operands are read in 4 gaps)");
 
 // The per-tile schedule of head dim D: kSec MFMAs per section, N = 4 kSec per tile (gaps 0..N-1).
@@ -150,35 +100,31 @@ template <class T>
 __device__ __forceinline__ void mf_zero(f32x16& d, const typename T::vec8& a, const typename T::vec8& b) {
 #if __HIP_DEVICE_COMPILE__
   if constexpr (std::is_same<T, BF16>::value)
-    asm volatile(KV_XNOP "v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
   else
-    asm volatile(KV_XNOP "v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
 #endif
 }
-// kSeed: the first MFMA of a dP chain, whose C operand (the -Delta seeds) may have been assembled by
-// VALU moves: always padded
-template <class T, bool kSeed = false>
+// No s_nop pads the asm MFMAs that read VALU-written registers (the packed P / dS, the -Delta seeds
+// that start a dP chain): the schedule places every such write >= 2 instructions before its MFMA,
+// which tools/diag/mfma_hazard_check.py verifies on the ISA in tests/test_codegen.py (an s_nop 1
+// ahead of each measured 2.2 % on the Wan backward, ahead of the S/dP MFMAs too 2 %).
+template <class T>
 __device__ __forceinline__ void mf_vacc(f32x16& d, const typename T::vec8& a, const typename T::vec8& b) {
 #if __HIP_DEVICE_COMPILE__
-  if constexpr (kSeed && !VB_KV128_XNOP) {
-    if constexpr (std::is_same<T, BF16>::value)
-      asm volatile(KV_YNOP "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    else
-      asm volatile(KV_YNOP "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-  } else if constexpr (std::is_same<T, BF16>::value) {
-    asm volatile(KV_XNOP "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-  } else {
-    asm volatile(KV_XNOP "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-  }
+  if constexpr (std::is_same<T, BF16>::value)
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
+  else
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
 #endif
 }
 template <class T>
 __device__ __forceinline__ void mf_aacc(f32x16& d, const typename T::vec8& a, const typename T::vec8& b) {
 #if __HIP_DEVICE_COMPILE__
   if constexpr (std::is_same<T, BF16>::value)
-    asm volatile(KV_YNOP "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
   else
-    asm volatile(KV_YNOP "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(d) : "v"(a), "v"(b));
 #endif
 }
 template <int kImm, class V>
@@ -380,13 +326,13 @@ __device__ __forceinline__ void qgap(f32x16& s, f32x16& dp, u32x4 (&pd)[2], floa
 
 }  // namespace kvp
 
-// D=128: one workgroup per CU (one wave per SIMD); D=64: VB_KV64_WAVES.
+// D=128: one workgroup per CU (one wave per SIMD); D=64: bwd::kKv64Waves.
 // kML: the multi-level backward's level-1 dK/dV (vb_ml_attn_bwd; bwd_dkdv_kernel<kPooled = false,
 // kML>): K/V are the pyramids' level-1 rows, a key block takes the q-blocks whose level for it is 1,
 // and each key adds the mean-pool adjoints of its level-2/4/8 pyramid rows (the reference kernel's
 // _bwd_kv epilogue, block_sparse_attn_kernel_with_backward_9_10.py:1494-1563).
 template <int D, class T, bool kPooled, bool kML = false>
-__global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) bwd_dkdv_pipe_kernel(const BwdParams p) {
+__global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : bwd::kKv64Waves) bwd_dkdv_pipe_kernel(const BwdParams p) {
   using namespace bwd;
   using namespace kvp;
   static_assert(!(kML && kPooled), "the multi-level pooled levels run bwd_dkdv_kernel's union walk");
@@ -405,35 +351,16 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
   const int half = lane >> 5;
   const int l32 = lane & 31;
 
-  // ---- work item: bwd_dkdv_kernel's mapping (heavy text columns first, then XCD-contiguous) ----
+  // ---- work item (dkdv_item: heavy text columns first, then XCD-contiguous) ----
   const int BH = p.B * p.H;
   const int nkb = kPooled ? p.nbkp : p.nbk;
   const int split = kPooled ? (int)blockIdx.x % p.psplit : 0;
   int bh, kblk;
-  if (kPooled) {
-    const int lin = (int)blockIdx.x / p.psplit;
-    bh = lin / nkb;
-    kblk = lin % nkb;
-  } else {
-    const int hr = kML ? 0 : min(p.heavy_rows, nkb);
-    const int n_heavy = hr * BH;
-    if ((int)blockIdx.x < n_heavy) {
-      kblk = nkb - 1 - (int)(blockIdx.x / BH);
-      bh = blockIdx.x % BH;
-    } else {
-      const int cols_left = nkb - hr;
-      const int lin = xcd_linear(blockIdx.x - n_heavy, cols_left * BH);
-      bh = lin / cols_left;
-      kblk = cols_left - 1 - lin % cols_left;
-    }
-  }
+  dkdv_item<kPooled, kML>(p, BH, nkb, bh, kblk);
   const int b = bh / p.H, h = bh % p.H;
-  int Lq = p.Lq, Lk = p.Lk;
-  int64_t qrow0 = 0, krow0 = 0;
-  if (p.cu_q) {
-    qrow0 = p.cu_q[b]; Lq = p.cu_q[b + 1] - p.cu_q[b];
-    krow0 = p.cu_k[b]; Lk = p.cu_k[b + 1] - p.cu_k[b];
-  }
+  int Lq, Lk;
+  int64_t qrow0, krow0;
+  seq_bounds(p, b, Lq, Lk, qrow0, krow0);
   const int Lkey = kPooled ? p.Lkp : Lk;
   const int k0 = kblk * kBlk;
   if (k0 >= Lkey) return;
@@ -544,7 +471,7 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
       int soff_q, soff_do, soff_st;
     };
     auto tile_dma = [&](int tt, int qb) __attribute__((always_inline)) -> TileDma {
-      const bool live = tt < ntiles && !(VB_KV128_NODMA && tt >= 3);
+      const bool live = tt < ntiles;
       const int row0 = qb * kBlk + (tt & 1) * kT;
       TileDma d;
       d.q = srd_t{qsrc, live ? qbytes : 0};
@@ -659,7 +586,7 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
             f32x16& s = sc == 0 ? s0 : s1;
             f32x16& dp = sc == 0 ? dp0 : dp1;
             constexpr int ks = i >> 1;
-            if constexpr (i & 1) mf_vacc<T, i == 1>(dp, a, vf[ks]);
+            if constexpr (i & 1) mf_vacc<T>(dp, a, vf[ks]);
             else if constexpr (ks == 0) mf_zero<T>(s, a, kf[0]);
             else mf_vacc<T>(s, a, kf[ks]);
           }
@@ -676,7 +603,7 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
         __builtin_amdgcn_sched_barrier(0);
         // ---- fillers of gap g ----
         constexpr int m = g + kLA;   // operand reads of MFMA m
-        if constexpr (m < N && !(VB_KV_ABL & 2)) {
+        if constexpr (m < N) {
           constexpr int ms = m / kSec, mi = m % kSec;
           if constexpr (ms == 0 || ms == 2) {
             rd128<u * TB + (ms >> 1) * 32 * RB + ((mi & 1) ? kDOImm : 0)>(xop[m], xa[(mi & 1) && !kShare][mi >> 1]);
@@ -717,21 +644,21 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
           rd128<un * TB + ((q & 1) ? kDOImm : 0)>(nx[q], xa[(q & 1) && !kShare][q >> 1]);
         }
         // ---- score arithmetic ----
-        if constexpr (!(VB_KV_ABL & 1) && mode != 2 && g >= S::kV0 && g < S::kV0 + S::kV0n) {
+        if constexpr (mode != 2 && g >= S::kV0 && g < S::kV0 + S::kV0n) {
           if constexpr (g == S::kV0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) launder(lq0[j]);
           }
           vgap<T, g - S::kV0, S::kV0n>(s0, dp0, lq0, pp0, pd0, c);
         }
-        if constexpr (!(VB_KV_ABL & 1) && mode != 2 && g >= S::kV1) {
+        if constexpr (mode != 2 && g >= S::kV1) {
           if constexpr (g == S::kV1) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) launder(lq1[j]);
           }
           vgap<T, g - S::kV1, S::kV1n>(s1, dp1, lq1, pp1, pd1, c);
         }
-        if constexpr (!(VB_KV_ABL & 1) && mode != 1 && g < S::kV1 + S::kV1n - N) vgap<T, g + N - S::kV1, S::kV1n>(s1, dp1, lq1, pp1, pd1, c);
+        if constexpr (mode != 1 && g < S::kV1 + S::kV1n - N) vgap<T, g + N - S::kV1, S::kV1n>(s1, dp1, lq1, pp1, pd1, c);
         // ---- barrier and the DMA of tile t+3 into the slot tile t-1 left ----
         if constexpr (mode != 2 && g == S::kV1) {
           launder(qb_raw);
@@ -739,10 +666,10 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
         }
         if constexpr (mode != 2 && g == S::kGb) {
           VB_WAIT_VMCNT(kPieces);   // tile t+1 landed (tile t+2 may be in flight)
-          if constexpr (!(VB_KV_ABL & 4)) __builtin_amdgcn_s_barrier();
+          __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
         }
-        if constexpr (!(VB_KV_ABL & 16) && mode != 2 && g >= S::kDma0 && g < S::kDma0 + kPieces) piece(dn, up, g - S::kDma0);
+        if constexpr (mode != 2 && g >= S::kDma0 && g < S::kDma0 + kPieces) piece(dn, up, g - S::kDma0);
         if constexpr (g == N - 1) {
 #pragma unroll
           for (int q = 0; q < kLA; ++q) launder(nx[q]);
@@ -921,11 +848,11 @@ __global__ void __launch_bounds__(bwd::kThreads, D == 128 ? 1 : VB_KV64_WAVES) b
 // 16-row quarters come from a per-tile table built in the prologue; a quarter past its level's list
 // and level-1 keys past L (without ref_tail) read as zero rows.
 template <int D, class T, bool kPool, int R, bool kML = false>
-__global__ void __launch_bounds__(bwd::kThreads, R == 2 ? (D == 128 ? (kML ? 1 : 2) : VB_DQ64_R2_WGS) : (D == 128 ? 1 : VB_KV64_WAVES))
+__global__ void __launch_bounds__(bwd::kThreads, R == 2 ? (D == 128 ? (kML ? 1 : 2) : bwd::kDq64R2Wgs) : (D == 128 ? 1 : bwd::kKv64Waves))
     bwd_dq_pipe_kernel(const BwdParams p) {
   using namespace bwd;
   using namespace kvp;
-  using S = QSched<D, R, R == 2 ? VB_DQ2_LA : kLA>;
+  using S = QSched<D, R, R == 2 ? bwd::kDq2LA : kvp::kLA>;
   using V8 = typename T::vec8;
   static_assert(!kML || (R == 2 && !kPool), "the multi-level dQ runs on the 2-slot ring, no pooled branch");
   constexpr int KS = S::KS, DT = S::DT, RB = S::RB, N = S::N, TB = S::kTileBytes;
@@ -944,27 +871,13 @@ __global__ void __launch_bounds__(bwd::kThreads, R == 2 ? (D == 128 ? (kML ? 1 :
   const int half = lane >> 5;
   const int l32 = lane & 31;
 
-  // heavy-first, then XCD-contiguous head-major (bwd_dq_kernel's mapping)
   const int BH = p.B * p.H;
-  const int hr = min(p.heavy_rows, p.nbq);
-  const int n_heavy = hr * BH;
   int qblk, bh;
-  if ((int)blockIdx.x < n_heavy) {
-    qblk = p.nbq - 1 - (int)(blockIdx.x / BH);
-    bh = blockIdx.x % BH;
-  } else {
-    const int rows_left = p.nbq - hr;
-    const int lin = xcd_linear(blockIdx.x - n_heavy, rows_left * BH);
-    bh = lin / rows_left;
-    qblk = rows_left - 1 - lin % rows_left;
-  }
+  dq_item(p, BH, bh, qblk);
   const int b = bh / p.H, h = bh % p.H;
-  int Lq = p.Lq, Lk = p.Lk;
-  int64_t qrow0 = 0, krow0 = 0;
-  if (p.cu_q) {
-    qrow0 = p.cu_q[b]; Lq = p.cu_q[b + 1] - p.cu_q[b];
-    krow0 = p.cu_k[b]; Lk = p.cu_k[b + 1] - p.cu_k[b];
-  }
+  int Lq, Lk;
+  int64_t qrow0, krow0;
+  seq_bounds(p, b, Lq, Lk, qrow0, krow0);
   const int q0 = qblk * kBlk;
   if (q0 >= Lq) return;
   const int nbk = (Lk + kBlk - 1) / kBlk;
@@ -1506,68 +1419,38 @@ __global__ void __launch_bounds__(bwd::kThreads, R == 2 ? (D == 128 ? (kML ? 1 :
     }
 }
 
-template <int D>
-static int launch_pipe(const BwdParams& p, bool pooled, bool f16, hipStream_t s) {
+// ---- launchers (vb_attn_bwd.hpp) ----------------------------------------------------------------
+int launch_dkdv_pipe(const BwdParams& p, int D, int dtype, bool pooled, hipStream_t s) {
   const int BH = p.B * p.H;
-  if (pooled) {
-    const dim3 grid(p.nbkp * BH * p.psplit);
-    if (f16) hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<D, F16, true>), grid, dim3(bwd::kThreads), 0, s, p);
-    else hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<D, BF16, true>), grid, dim3(bwd::kThreads), 0, s, p);
-    return check_launch("bwd_dkdv_pipe_kernel<pooled>");
-  }
-  const dim3 grid(p.nbk * BH);
-  if (f16) hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<D, F16, false>), grid, dim3(bwd::kThreads), 0, s, p);
-  else hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<D, BF16, false>), grid, dim3(bwd::kThreads), 0, s, p);
-  return check_launch("bwd_dkdv_pipe_kernel");
+  const dim3 grid(pooled ? p.nbkp * BH * p.psplit : p.nbk * BH);
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto pl) {
+    hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<d(), decltype(t), pl()>), grid, dim3(bwd::kThreads), 0, s, p);
+    return check_launch(pl() ? "bwd_dkdv_pipe_kernel<pooled>" : "bwd_dkdv_pipe_kernel");
+  }, pooled);
 }
 
-template <int D, int R>
-static int launch_dq(const BwdParams& p, bool pool, bool f16, hipStream_t s) {
-  const dim3 grid(p.nbq * p.B * p.H);
-  if (pool) {
-    if (f16) hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, F16, true, R>), grid, dim3(bwd::kThreads), 0, s, p);
-    else hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, BF16, true, R>), grid, dim3(bwd::kThreads), 0, s, p);
-  } else {
-    if (f16) hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, F16, false, R>), grid, dim3(bwd::kThreads), 0, s, p);
-    else hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, BF16, false, R>), grid, dim3(bwd::kThreads), 0, s, p);
-  }
-  return check_launch("bwd_dq_pipe_kernel");
+int launch_dq_pipe(const BwdParams& p, int D, int dtype, bool pool, bool ring4, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto pl, auto r4) {
+    hipLaunchKernelGGL((bwd_dq_pipe_kernel<d(), decltype(t), pl(), r4() ? 4 : 2>), dim3(p.nbq * p.B * p.H),
+                       dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dq_pipe_kernel");
+  }, pool, ring4);
 }
 
-// ring slots: VB_BWD_DQ{64,128}_RING by default, 4 with VB_BWD_SEL_DQ_RING4
-int launch_dq_pipe(const BwdParams& p, int D, bool pool, bool f16, hipStream_t s, int sel, int& ran) {
-  const bool ring4 = (sel & VB_BWD_SEL_DQ_RING4) || (D == 64 ? VB_BWD_DQ64_RING : VB_BWD_DQ128_RING) != 2;
-  ran |= ring4 ? VB_BWD_RAN_DQ_PIPE_RING4 : VB_BWD_RAN_DQ_PIPE_RING2;
-  if (D == 64) return ring4 ? launch_dq<64, 4>(p, pool, f16, s) : launch_dq<64, 2>(p, pool, f16, s);
-  return ring4 ? launch_dq<128, 4>(p, pool, f16, s) : launch_dq<128, 2>(p, pool, f16, s);
+int launch_ml_dkdv_pipe(const BwdParams& p, int D, int dtype, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t) {
+    hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<d(), decltype(t), false, true>), dim3(p.nbk * p.B * p.H),
+                       dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dkdv_pipe_kernel<multi-level>");
+  });
 }
 
-int launch_ml_dkdv_pipe(const BwdParams& p, int D, bool f16, hipStream_t s) {
-  const dim3 grid(p.nbk * p.B * p.H);
-  if (D == 128) {
-    if (f16) hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<128, F16, false, true>), grid, dim3(bwd::kThreads), 0, s, p);
-    else hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<128, BF16, false, true>), grid, dim3(bwd::kThreads), 0, s, p);
-  } else {
-    if (f16) hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<64, F16, false, true>), grid, dim3(bwd::kThreads), 0, s, p);
-    else hipLaunchKernelGGL((bwd_dkdv_pipe_kernel<64, BF16, false, true>), grid, dim3(bwd::kThreads), 0, s, p);
-  }
-  return check_launch("bwd_dkdv_pipe_kernel<multi-level>");
-}
-
-template <int D>
-static int launch_ml_dq(const BwdParams& p, bool f16, hipStream_t s) {
-  const dim3 grid(p.nbq * p.B * p.H);
-  if (f16) hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, F16, false, 2, true>), grid, dim3(bwd::kThreads), 0, s, p);
-  else hipLaunchKernelGGL((bwd_dq_pipe_kernel<D, BF16, false, 2, true>), grid, dim3(bwd::kThreads), 0, s, p);
-  return check_launch("bwd_dq_pipe_kernel<multi-level>");
-}
-
-int launch_ml_dq_pipe(const BwdParams& p, int D, bool f16, hipStream_t s) {
-  return D == 128 ? launch_ml_dq<128>(p, f16, s) : launch_ml_dq<64>(p, f16, s);
-}
-
-int launch_dkdv_pipe(const BwdParams& p, int D, bool pooled, bool f16, hipStream_t s) {
-  return D == 128 ? launch_pipe<128>(p, pooled, f16, s) : launch_pipe<64>(p, pooled, f16, s);
+int launch_ml_dq_pipe(const BwdParams& p, int D, int dtype, hipStream_t s) {
+  return dispatch_head(D, dtype, [&](auto d, auto t) {
+    hipLaunchKernelGGL((bwd_dq_pipe_kernel<d(), decltype(t), false, 2, true>), dim3(p.nbq * p.B * p.H),
+                       dim3(bwd::kThreads), 0, s, p);
+    return check_launch("bwd_dq_pipe_kernel<multi-level>");
+  });
 }
 
 }  // namespace vb

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "vb_args.hpp"
 #include "vb_attn_fwd.hpp"
 #include "vb_trace.hpp"
 
@@ -1156,36 +1157,21 @@ static int launch_one(FwdParams p, hipStream_t stream, const char* what) {
   return check_launch(what);
 }
 
-template <int D, class T>
-static int launch_fwd(const FwdParams& p, bool pool, hipStream_t stream) {
-  const bool rows = p.kv_rows != nullptr;
-  const bool cbias = VB_FWD_CBIAS && p.lse == nullptr;
-  const char* w = "attn_fwd_kernel";
-  if (cbias && pool && rows) return launch_one<attn_fwd_kernel<D, T, true, true, false, true, false>, attn_fwd_kernel<D, T, true, true, false, true, true>>(p, stream, w);
-  if (cbias && rows) return launch_one<attn_fwd_kernel<D, T, false, true, false, true, false>, attn_fwd_kernel<D, T, false, true, false, true, true>>(p, stream, w);
-  if (cbias && pool) return launch_one<attn_fwd_kernel<D, T, true, false, false, true, false>, attn_fwd_kernel<D, T, true, false, false, true, true>>(p, stream, w);
-  if (cbias) return launch_one<attn_fwd_kernel<D, T, false, false, false, true, false>, attn_fwd_kernel<D, T, false, false, false, true, true>>(p, stream, w);
-  if (pool && rows) return launch_one<attn_fwd_kernel<D, T, true, true, false, false, false>, attn_fwd_kernel<D, T, true, true, false, false, true>>(p, stream, w);
-  if (pool) return launch_one<attn_fwd_kernel<D, T, true, false, false, false, false>, attn_fwd_kernel<D, T, true, false, false, false, true>>(p, stream, w);
-  if (rows) return launch_one<attn_fwd_kernel<D, T, false, true, false, false, false>, attn_fwd_kernel<D, T, false, true, false, false, true>>(p, stream, w);
-  return launch_one<attn_fwd_kernel<D, T, false, false, false, false, false>, attn_fwd_kernel<D, T, false, false, false, false, true>>(p, stream, w);
+// one forward kernel: its plain and its persistent instantiation (launch_one picks by p.work_queue)
+template <int D, class T, bool kPool, bool kKvRows, bool kML, bool kCBias>
+static int launch_attn(const FwdParams& p, hipStream_t stream, const char* what) {
+  return launch_one<attn_fwd_kernel<D, T, kPool, kKvRows, kML, kCBias, false>,
+                    attn_fwd_kernel<D, T, kPool, kKvRows, kML, kCBias, true>>(p, stream, what);
 }
 
 static int dispatch_fwd(const FwdParams& p, int D, int dtype, bool pool, hipStream_t stream) {
-  if (dtype == VB_DTYPE_BF16) {
-    if (D == 64) return launch_fwd<64, BF16>(p, pool, stream);
-    if (D == 128) return launch_fwd<128, BF16>(p, pool, stream);
-  } else if (dtype == VB_DTYPE_F16) {
-    if (D == 64) return launch_fwd<64, F16>(p, pool, stream);
-    if (D == 128) return launch_fwd<128, F16>(p, pool, stream);
-  } else {
-    return fail(VB_ERR_INVALID, "attn: unknown dtype");
-  }
-  return fail(VB_ERR_UNSUPPORTED, "attn: head_dim must be 64 or 128, got " + std::to_string(D));
+  if (!dtype_ok(dtype)) return fail(VB_ERR_INVALID, "attn: unknown dtype");
+  if (!head_dim_ok(D)) return fail(VB_ERR_UNSUPPORTED, "attn: head_dim must be 64 or 128, got " + std::to_string(D));
+  const bool cbias = VB_FWD_CBIAS && p.lse == nullptr;
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto pl, auto rows, auto cb) {
+    return launch_attn<d(), decltype(t), pl(), rows(), false, cb()>(p, stream, "attn_fwd_kernel");
+  }, pool, p.kv_rows != nullptr, cbias);
 }
-
-static bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 
 }  // namespace vb
 
@@ -1225,10 +1211,9 @@ extern "C" int vb_attn_fwd(const vb_attn_args* a, void* stream) {
   if ((a->use_main && (a->k_stride[2] * 2 >= (1 << 24) || a->v_stride[2] * 2 >= (1 << 24))) ||
       (pool && (a->kp_stride[2] * 2 >= (1 << 24) || a->vp_stride[2] * 2 >= (1 << 24))))
     return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: k/v/kp/vp row strides must be < 2^24 bytes");
-  const int64_t kLim = int64_t(1) << 31;   // one (b,h) slice must be addressable by a 32-bit buffer offset
-  if (a->use_main && ((int64_t)(a->Lk - 1) * 2 * (a->k_stride[2] > a->v_stride[2] ? a->k_stride[2] : a->v_stride[2]) + 2 * a->D >= kLim))
+  if (a->use_main && (!slice_fits32(a->Lk, a->k_stride[2], a->D) || !slice_fits32(a->Lk, a->v_stride[2], a->D)))
     return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: a k/v (b,h) slice spans >= 2 GiB");
-  if (pool && ((int64_t)(a->Lkp - 1) * 2 * (a->kp_stride[2] > a->vp_stride[2] ? a->kp_stride[2] : a->vp_stride[2]) + 2 * a->D >= kLim))
+  if (pool && (!slice_fits32(a->Lkp, a->kp_stride[2], a->D) || !slice_fits32(a->Lkp, a->vp_stride[2], a->D)))
     return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: a kp/vp (b,h) slice spans >= 2 GiB");
   if (!aligned16(a->q) || !aligned16(a->out) || (a->use_main && (!aligned16(a->k) || !aligned16(a->v))) ||
       (pool && (!aligned16(a->kp) || !aligned16(a->vp))))
@@ -1248,8 +1233,7 @@ extern "C" int vb_attn_fwd(const vb_attn_args* a, void* stream) {
   p.out = a->out; p.lse = a->lse;
   p.lse_s[0] = (int64_t)a->H * a->Lq; p.lse_s[1] = a->Lq;
   p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->use_main ? a->Lk : 1; p.nbq = nbq; p.nbk = nbk;
-  const float scale = a->scale > 0.f ? a->scale : (float)(1.0 / sqrt((double)a->D));
-  p.c = scale * kLog2e;
+  p.c = scale_or_default(a->scale, a->D) * kLog2e;
   p.heavy_rows = a->heavy_rows;
 #if VB_DIAG
   if (const char* d = getenv("VB_DEBUG_ATTN")) p.dbg = atoi(d);
@@ -1281,7 +1265,7 @@ extern "C" int vb_ml_attn_fwd(const vb_ml_attn_args* a, void* stream) {
   if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: B, H, L must be positive");
   if (!a->q || !a->kpyr || !a->vpyr || !a->level_mask || !a->out)
     return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: missing q/kpyr/vpyr/level_mask/out");
-  if (a->D != 64 && a->D != 128)
+  if (!head_dim_ok(a->D))
     return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_fwd: head_dim must be 64 or 128, got " + std::to_string(a->D));
   const int nb = (a->L + kQBlk - 1) / kQBlk;
   if (nb > kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_fwd: L too long");
@@ -1307,26 +1291,15 @@ extern "C" int vb_ml_attn_fwd(const vb_ml_attn_args* a, void* stream) {
   p.B = a->B; p.H = a->H; p.Lq = a->L; p.Lk = a->L; p.nbq = nb; p.nbk = nb;
   p.Lpad = nb * kQBlk;
   p.ref_tail = a->ref_tail ? 1 : 0;
-  const float scale = a->scale > 0.f ? a->scale : (float)(1.0 / sqrt((double)a->D));
-  p.c = scale * kLog2e;
+  p.c = scale_or_default(a->scale, a->D) * kLog2e;
   p.heavy_rows = a->heavy_rows;
   p.work_queue = a->work_queue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool cb = VB_FWD_CBIAS && p.lse == nullptr;   // inference launches (see kCBias)
-  const char* w = "attn_fwd_kernel (multi-level)";
-  if (a->dtype == VB_DTYPE_BF16) {
-    if (a->D == 64 && cb) return launch_one<attn_fwd_kernel<64, BF16, false, false, true, true, false>, attn_fwd_kernel<64, BF16, false, false, true, true, true>>(p, st, w);
-    if (a->D == 64) return launch_one<attn_fwd_kernel<64, BF16, false, false, true, false, false>, attn_fwd_kernel<64, BF16, false, false, true, false, true>>(p, st, w);
-    if (cb) return launch_one<attn_fwd_kernel<128, BF16, false, false, true, true, false>, attn_fwd_kernel<128, BF16, false, false, true, true, true>>(p, st, w);
-    return launch_one<attn_fwd_kernel<128, BF16, false, false, true, false, false>, attn_fwd_kernel<128, BF16, false, false, true, false, true>>(p, st, w);
-  }
-  if (a->dtype == VB_DTYPE_F16) {
-    if (a->D == 64 && cb) return launch_one<attn_fwd_kernel<64, F16, false, false, true, true, false>, attn_fwd_kernel<64, F16, false, false, true, true, true>>(p, st, w);
-    if (a->D == 64) return launch_one<attn_fwd_kernel<64, F16, false, false, true, false, false>, attn_fwd_kernel<64, F16, false, false, true, false, true>>(p, st, w);
-    if (cb) return launch_one<attn_fwd_kernel<128, F16, false, false, true, true, false>, attn_fwd_kernel<128, F16, false, false, true, true, true>>(p, st, w);
-    return launch_one<attn_fwd_kernel<128, F16, false, false, true, false, false>, attn_fwd_kernel<128, F16, false, false, true, false, true>>(p, st, w);
-  }
-  return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: unknown dtype");
+  if (!dtype_ok(a->dtype)) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: unknown dtype");
+  return dispatch_head(a->D, a->dtype, [&](auto d, auto t, auto cbias) {
+    return launch_attn<d(), decltype(t), false, false, true, cbias()>(p, st, "attn_fwd_kernel (multi-level)");
+  }, cb);
 }
 
 extern "C" int vb_block_sparse_attn_fwd(const void* q_unpad, const void* k_unpad, const void* v_unpad,
@@ -1350,7 +1323,7 @@ extern "C" int vb_block_sparse_attn_fwd(const void* q_unpad, const void* k_unpad
   const int nbq = (max_seqlen_q + kQBlk - 1) / kQBlk;
   const int nbk = (max_seqlen_k + kQBlk - 1) / kQBlk;
   if (nbk > kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: max_seqlen_k too long");
-  if ((int64_t)(max_seqlen_k - 1) * 2 * num_heads * head_dim + 2 * head_dim >= (int64_t(1) << 31))
+  if (!slice_fits32(max_seqlen_k, (int64_t)num_heads * head_dim, head_dim))
     return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: a sequence's k/v span >= 2 GiB");
   FwdParams p{};
   p.q = q_unpad; p.k = k_unpad; p.v = v_unpad;
@@ -1370,7 +1343,6 @@ extern "C" int vb_block_sparse_attn_fwd(const void* q_unpad, const void* k_unpad
   p.out = out_unpad; p.lse = softmax_lse;
   p.lse_s[0] = (int64_t)num_heads * max_seqlen_q; p.lse_s[1] = max_seqlen_q;
   p.B = batch; p.H = num_heads; p.Lq = max_seqlen_q; p.Lk = max_seqlen_k; p.nbq = nbq; p.nbk = nbk;
-  const float scale = softmax_scale > 0.f ? softmax_scale : (float)(1.0 / sqrt((double)head_dim));
-  p.c = scale * kLog2e;
+  p.c = scale_or_default(softmax_scale, head_dim) * kLog2e;
   return dispatch_fwd(p, head_dim, dtype, false, reinterpret_cast<hipStream_t>(stream));
 }

@@ -264,7 +264,7 @@ __global__ void __launch_bounds__(kPThreads, kPMinWg) mask_predict_kernel(const 
   // and date from a build with two groups per wave; they stay because hipcc's code depends on them:
   // taking out any of six of the nine changes the kernel's instruction stream (the one round the
   // epilogue call by 2900 lines at kKeep 32), and the refactor that fixed the knobs was held to an
-  // unchanged listing (tools/diag/pred_listing_diff.py). Remove them together with a timed A/B.
+  // unchanged listing (tools/diag/listing_diff.py). Remove them together with a timed A/B.
   constexpr int KQ = 1;
   // R stores per wave and LDS tile: one per pair of 32-key tiles; at 16 one per 32-key tile
   constexpr int kSt = kKeep == 16 ? kKT : KQ * (kKT / 2);
