@@ -626,6 +626,65 @@ int vb_judge_sparsity(const vb_judge_args* args, void* stream);
 int vb_head_budget(const float* sparsity, int B, int H, int nb, double base, double lo, double hi,
                    int arith, int32_t* max_keep, float* ratio, void* stream);
 
+/* ==========================================================================================
+ * Attention-recall probe: what a block mask keeps of the true attention, measured on a call's own
+ * q, k and mask for S probe queries per head. Additive to ABI 4.
+ *
+ * The energy rule steers one quantity through a sampled, pooled proxy: the share of a query's
+ * softmax mass that falls inside the key blocks its mask row keeps. vb_mask_recall computes that
+ * share exactly (recall), and the best share any mask with the same number of blocks could have kept
+ * for that query (oracle recall). Both low: the budget is too small. Recall well below the oracle:
+ * the predictor picked the wrong blocks.
+ *
+ * All arithmetic fp32 unless stated. For every (b,h) and probe r < S:
+ *   g = clamp(probe_pos[r], 0, L-1), a REORDERED position; i = g / 128 its mask row
+ *   the query is caller row rows[g]; key j of the reordered sequence is caller row rows[j],
+ *   j = 0 .. L-1 (rows NULL: the identity). Only the L real keys take part: the last block holds
+ *   L - 128*(nb-1) keys, no replicate padding.
+ *   s_j = scale * <q, k_j>, MFMA with fp32 accumulation; e_j = exp2((s_j - max_j s_j) * log2(e))
+ *   (evaluated per block relative to the block's maximum and rescaled to the row's)
+ *   E_c = sum of e_j over the keys of block c (an order fixed by the shape)
+ *   T = sum_c E_c;  K = sum of E_c over the c with mask[b,h,i,c] != 0: BOTH summed over c in
+ *   ascending block order, so an all-ones mask row gives K == T in bits and recall exactly 1.0f
+ *   row_recall = K / T;  row_kept = n_i = #{c < nb : mask[b,h,i,c] != 0}
+ *   row_oracle = (the sum of the n_i largest E_c) / T: ties take the lower block index first, the
+ *   selected set is summed in ascending block order; a mask row that already holds the n_i heaviest
+ *   blocks gives row_oracle == row_recall in bits; n_i = 0 gives 0 for both
+ *   recall[b,h], oracle_recall[b,h] = the fp32 means over r, summed serially in r order
+ * q, k: as vb_judge_args. rows: the array vb_attn_args.q_rows / kv_rows take (a permutation of
+ * [0, L); the kernel clamps what it reads to [0, L-1] before it is used as an address). probe_pos:
+ * DEVICE int32 [S], shared by all (b,h), S in [1, 64]; clamped to [0, L-1] by the kernel before any
+ * use. block_mask: uint8 [B,H,nb,nb] in reordered order, nb = ceil(L/128), unit stride along the key
+ * blocks, the other three strides in mask_stride (a head stride of 0 is the shared_head0 view).
+ * Null q, k, probe_pos, block_mask or recall, bad sizes, S outside [1, 64], an unknown dtype, q/k
+ * bases not 16-byte aligned or strides that are not non-negative multiples of 8, negative mask
+ * strides and a short or missing workspace are VB_ERR_INVALID before any launch; D not 64 or 128,
+ * L > 131072 and a (b,h) slice of 2 GiB or more are VB_ERR_UNSUPPORTED.
+ * workspace: device, 16-byte aligned, >= vb_mask_recall_workspace_size(args) bytes (host arithmetic:
+ * B*H*S*nb pairs of fp32, a block's maximum and its sum relative to it, staged between the launches,
+ * plus B*H*S pairs of row results: at most 512 KiB + 512 bytes per head).
+ * Deterministic: no floating-point atomics, every sum in an order fixed by the shape; two calls give
+ * the same bits. Three launches on `stream`; nothing is allocated, nothing synchronises.
+ * ========================================================================================== */
+typedef struct vb_recall_args {
+  const void* q; const void* k;
+  int64_t q_stride[3]; int64_t k_stride[3];
+  const int32_t* rows;       /* device [L]: reordered position -> caller row, or NULL = identity */
+  const int32_t* probe_pos;  /* device [S]: reordered positions of the probe queries */
+  const uint8_t* block_mask; int64_t mask_stride[3];
+  int B, H, L, D, S;
+  float scale;               /* <= 0 -> D^-1/2 */
+  int dtype;
+  float* recall;             /* [B,H] */
+  float* oracle_recall;      /* [B,H] or NULL */
+  float* row_recall;         /* [B,H,S] or NULL */
+  float* row_oracle;         /* [B,H,S] or NULL */
+  int32_t* row_kept;         /* [B,H,S] or NULL: kept blocks in the probe row's mask row */
+  void* workspace; uint64_t workspace_bytes;
+} vb_recall_args;
+uint64_t vb_mask_recall_workspace_size(const vb_recall_args* args);
+int vb_mask_recall(const vb_recall_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

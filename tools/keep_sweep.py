@@ -10,7 +10,12 @@ keep 32, the kept-block fraction, the share of mask entries equal to the keep-32
 seed (the same 128 uniforms per (b,h): the top 16 are a prefix of the top 32), and the PSNR of the
 module output against dense SDPA on the same inputs.
 
-usage: python tools/keep_sweep.py [--variant cog|wan|both] [--rounds 15] [--out FILE.json]"""
+--recall appends, per density, the attention recall of its mask and the oracle recall of its budget
+(ops.mask_recall on the same q, k and mask: 30 probe queries per head, the module option's own
+positions; mean and smallest head), and one more module, keep 32 with probe="recall", whose call time
+against keep 32 is what the option costs. The other columns are computed as without the flag.
+
+usage: python tools/keep_sweep.py [--variant cog|wan|both] [--rounds 15] [--recall] [--out FILE.json]"""
 import argparse
 import json
 import math
@@ -47,13 +52,27 @@ def timed(fn, reps=5):
     return e0.elapsed_time(e1) / reps
 
 
-def sweep(variant, rounds, dev):
+def recall_of(m, q, k, pos):
+    """Recall and oracle recall of the module's last mask as its attention launch read it."""
+    mask = m.last_mask
+    if m.mask_head_mode == "shared_head0":
+        mask = mask[:, :1].expand_as(mask)
+    rec, ora = ops.mask_recall(q, k, mask, pos, rows=m._rows(q.device))
+    return {"recall_mean": rec.mean().item(), "recall_min_head": rec.min().item(),
+            "oracle_recall_mean": ora.mean().item(), "oracle_recall_min_head": ora.min().item()}
+
+
+def sweep(variant, rounds, dev, recall=False):
     H, D = (48, 64) if variant == "cog" else (12, 128)
     q, k, v = local_qkv(variant, H, D, 0, dev)
     L = q.shape[2]
     # labels: the three densities and a second keep-32 module (the A/A spread of every column)
     mods = {str(kp): vblade.AdaptiveBlockSparseAttn(variant, log_every=0, num_keep=kp) for kp in KEEPS}
     mods["32#aa"] = vblade.AdaptiveBlockSparseAttn(variant, log_every=0, num_keep=32)
+    pos = None
+    if recall:
+        mods["32+probe"] = vblade.AdaptiveBlockSparseAttn(variant, log_every=0, num_keep=32, probe="recall")
+        pos = mods["32+probe"].probe_pos.to(dev)
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     res, masks = {}, {}
 
@@ -83,6 +102,8 @@ def sweep(variant, rounds, dev):
             masks[lab] = mask
             res[lab] = {"num_keep": m.num_keep, "kept_fraction": mask.float().mean().item(),
                         "psnr_vs_dense_db": psnr(out, dense)}
+            if recall:
+                res[lab].update(recall_of(m, q, k, pos))
             for f in ("pred_fused_ms", "pred_scores_ms"):
                 work[lab][f]()
         times = {lab: {f: [] for f in work[lab]} for lab in mods}
@@ -107,19 +128,25 @@ def main():
     ap.add_argument("--variant", default="both")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--recall", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda")
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
-        r = sweep(variant, a.rounds, dev)
+        r = sweep(variant, a.rounds, dev, a.recall)
         out["results"].append(r)
         print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks)")
-        print("  keep | fused pred ms (x32) | scores-only ms (x32) | call ms (x32) | kept | == keep32 | PSNR dB")
+        print("  keep | fused pred ms (x32) | scores-only ms (x32) | call ms (x32) | kept | == keep32 | PSNR dB"
+              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else ""))
         for lab, d in r["densities"].items():
+            extra = ""
+            if a.recall:
+                extra = (f" | {d['recall_mean']:.4f} ({d['recall_min_head']:.4f}) | "
+                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})")
             print(f"  {lab:>5} | {d['pred_fused_ms']:.4f} ({d['pred_fused_vs_keep32']:.3f}) | "
                   f"{d['pred_scores_ms']:.4f} ({d['pred_scores_vs_keep32']:.3f}) | "
                   f"{d['call_ms']:.4f} ({d['call_vs_keep32']:.3f}) | {d['kept_fraction']:.4f} | "
-                  f"{d['mask_equal_to_keep32']:.4f} | {d['psnr_vs_dense_db']:.2f}", flush=True)
+                  f"{d['mask_equal_to_keep32']:.4f} | {d['psnr_vs_dense_db']:.2f}{extra}", flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

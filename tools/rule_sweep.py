@@ -16,7 +16,13 @@ heads), which gives the heads different concentrations. Per setting: the predict
 riding), the whole module call and its ratio to the default, the kept-block fraction, and the PSNR
 of the module output against dense SDPA on the same inputs.
 
-usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--out FILE.json]
+--recall appends, per setting, the attention recall of its mask and the oracle recall of its budget
+(ops.mask_recall on the same q, k and mask: 30 probe queries per head, the module option's own
+positions; mean and smallest head), and one more setting, `energy/probe=recall`, whose call time
+against `energy` is what the option costs, beside `judge`'s. The other columns are computed as
+without the flag.
+
+usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--recall] [--out FILE.json]
        rocprofv3 --kernel-trace --stats -d DIR -- python tools/rule_sweep.py --variant cog --one-call SETTING
        (four module calls of one setting and nothing else: a kernel trace then shows its launches
        per call, tools/kstats.py DIR)"""
@@ -57,7 +63,17 @@ def timed(fn, reps=5):
     return e0.elapsed_time(e1) / reps
 
 
-def settings(variant, H):
+def recall_of(m, q, k, pos):
+    """Recall and oracle recall of the module's last mask as its attention launch read it."""
+    mask = m.last_mask
+    if m.mask_head_mode == "shared_head0":
+        mask = mask[:, :1].expand_as(mask)
+    rec, ora = ops.mask_recall(q, k, mask, pos, rows=m._rows(q.device))
+    return {"recall_mean": rec.mean().item(), "recall_min_head": rec.min().item(),
+            "oracle_recall_mean": ora.mean().item(), "oracle_recall_min_head": ora.min().item()}
+
+
+def settings(variant, H, recall=False):
     d = VARIANT_DEFAULTS[variant]
     mk = lambda **kw: vblade.AdaptiveBlockSparseAttn(variant, log_every=0, **kw)  # noqa: E731
     mods = {"energy": mk(), "energy#aa": mk()}
@@ -72,6 +88,8 @@ def settings(variant, H):
     mods["judge"] = mk(head_budget="judge")
     r = d["max_retain_ratio"]
     mods["judge/clamp(r,r)"] = mk(head_budget="judge", judge_clamp=(r, r))
+    if recall:
+        mods["energy/probe=recall"] = mk(probe="recall")
     return mods
 
 
@@ -83,11 +101,12 @@ def inputs(variant, H, D, dev, temps):
     return q, k, v
 
 
-def sweep(variant, rounds, dev, temps=None):
+def sweep(variant, rounds, dev, temps=None, recall=False):
     H, D = (48, 64) if variant == "cog" else (12, 128)
     q, k, v = inputs(variant, H, D, dev, temps)
     L = q.shape[2]
-    mods = settings(variant, H)
+    mods = settings(variant, H, recall)
+    pos = mods["energy/probe=recall"].probe_pos.to(dev) if recall else None
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     res = {}
 
@@ -110,6 +129,8 @@ def sweep(variant, rounds, dev, temps=None):
             out = work[lab]["call_ms"]()
             torch.cuda.synchronize()
             res[lab] = {"kept_fraction": m.last_mask.float().mean().item(), "psnr_vs_dense_db": psnr(out, dense)}
+            if recall:
+                res[lab].update(recall_of(m, q, k, pos))
             if m.head_budget == "judge":
                 b = m.last_head_budget.flatten().tolist()
                 sp = m.last_head_sparsity.flatten().tolist()
@@ -140,12 +161,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--one-call", default=None, metavar="SETTING")
     ap.add_argument("--head-temps", type=float, nargs=2, default=None, metavar=("LO", "HI"))
+    ap.add_argument("--recall", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.one_call:
         variant = "cog" if a.variant == "both" else a.variant
         H, D = (48, 64) if variant == "cog" else (12, 128)
-        m = settings(variant, H)[a.one_call]
+        m = settings(variant, H, a.recall)[a.one_call]
         q, k, v = inputs(variant, H, D, dev, a.head_temps)
         with torch.no_grad():
             for _ in range(4):
@@ -155,15 +177,19 @@ def main():
         return
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
-        r = sweep(variant, a.rounds, dev, a.head_temps)
+        r = sweep(variant, a.rounds, dev, a.head_temps, a.recall)
         out["results"].append(r)
         print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks), inputs {r['inputs']}; "
               f"judge/clamp(r,r) mask == energy/uniform[H] mask: {r['clamp_rr_mask_equals_uniform']}")
-        print("  setting                      | fused pred ms (x energy) | call ms (x energy, x uniform[H]) | kept   | PSNR dB")
+        print("  setting                      | fused pred ms (x energy) | call ms (x energy, x uniform[H]) | kept   | PSNR dB"
+              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else ""))
         for lab, d in r["settings"].items():
             extra = ""
+            if a.recall:
+                extra = (f" | {d['recall_mean']:.4f} ({d['recall_min_head']:.4f}) | "
+                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})")
             if "head_budget_min" in d:
-                extra = (f" | budgets {d['head_budget_min']}..{d['head_budget_max']} (mean {d['head_budget_mean']:.2f}), "
+                extra += (f" | budgets {d['head_budget_min']}..{d['head_budget_max']} (mean {d['head_budget_mean']:.2f}), "
                          f"sparsity {d['head_sparsity_min']:.3f}..{d['head_sparsity_max']:.3f}")
             print(f"  {lab:<28} | {d['pred_fused_ms']:.4f} ({d['pred_fused_vs_energy']:.3f}) | "
                   f"{d['call_ms']:.4f} ({d['call_vs_energy']:.3f}, {d['call_vs_uniform']:.3f}) | {d['kept_fraction']:.4f} | "

@@ -199,7 +199,25 @@ class JudgeArgs(ctypes.Structure):
     ]
 
 
+class RecallArgs(ctypes.Structure):
+    """vb_recall_args (include/vblade.h)."""
+    _fields_ = [
+        ("q", _vp), ("k", _vp),
+        ("q_stride", _i64x3), ("k_stride", _i64x3),
+        ("rows", _vp), ("probe_pos", _vp),
+        ("block_mask", _vp), ("mask_stride", _i64x3),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("L", ctypes.c_int), ("D", ctypes.c_int),
+        ("S", ctypes.c_int),
+        ("scale", ctypes.c_float),
+        ("dtype", ctypes.c_int),
+        ("recall", _vp), ("oracle_recall", _vp),
+        ("row_recall", _vp), ("row_oracle", _vp), ("row_kept", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 VB_JUDGE_MAX_SAMPLES = 64
+VB_RECALL_MAX_SAMPLES = 64
 VB_QK_BWD_MAX_GRID = 1024
 VB_QK_NORM_NONE, VB_QK_NORM_LAYER_HEAD, VB_QK_NORM_RMS_ROW = 0, 1, 2
 VB_QK_ROPE_NONE, VB_QK_ROPE_REAL, VB_QK_ROPE_COMPLEX = 0, 1, 2
@@ -267,6 +285,8 @@ SIGNATURES = {
     "vb_head_budget": (ctypes.c_int, [
         _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
         ctypes.c_int, _vp, _vp, _vp]),
+    "vb_mask_recall_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(RecallArgs)]),
+    "vb_mask_recall": (ctypes.c_int, [ctypes.POINTER(RecallArgs), _vp]),
 }
 
 _lib = None

@@ -152,6 +152,14 @@ class AdaptiveBlockSparseAttn(nn.Module):
     non-persistent buffer ``judge_rows``, which may be overwritten; ``forward(judge_rows=...)``
     overrides it for one call), so a call consumes no random numbers. ``last_head_sparsity`` (fp32
     [B,H]) and ``last_head_budget`` (int32 [B,H]) stay on the device.
+    probe: None (default) or "recall": every ``probe_every``-th call measures, on its own q, k and the
+    mask its attention launch uses (predicted or given, the shared_head0 view included), the exact
+    share of the softmax mass the mask keeps for ``probe_samples`` probe queries per head, and the
+    best share a mask with as many blocks could have kept (ops.mask_recall). ``last_recall`` and
+    ``last_oracle_recall`` (fp32 [B,H]) stay on the device; ``recall`` reads the running means. The
+    probe positions are drawn once, at construction, from a CPU generator seeded with ``probe_seed``
+    (distinct reordered positions of the video part; the non-persistent buffer ``probe_pos``, which
+    may be overwritten). Output, mask and random stream are those of a module without the option.
     """
 
     def __init__(self, variant: str = "cog", *, combine: str = "fused", **overrides):
@@ -162,7 +170,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
         unknown = set(overrides) - set(cfg) - {"energy_threshold", "block", "num_keep", "overlap", "gather_kv",
                                                "mask_head_mode", "order", "order_window", "persistent",
                                                "mask_mode", "init_k", "head_budget", "judge_samples",
-                                               "judge_key_stride", "judge_top", "judge_clamp", "judge_seed"}
+                                               "judge_key_stride", "judge_top", "judge_clamp", "judge_seed",
+                                               "probe", "probe_samples", "probe_seed", "probe_every"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
@@ -216,6 +225,32 @@ class AdaptiveBlockSparseAttn(nn.Module):
             gen.manual_seed(self.judge_seed)
             probe = self.text_length + torch.randperm(video, generator=gen)[:self.judge_samples]
             self.register_buffer("judge_rows", probe.to(torch.int32), persistent=False)
+        self.probe = cfg.get("probe")
+        self.probe_samples = int(cfg.get("probe_samples", 30))
+        self.probe_seed = int(cfg.get("probe_seed", 0))
+        self.probe_every = int(cfg.get("probe_every", 1))
+        self.last_recall: Optional[torch.Tensor] = None
+        self.last_oracle_recall: Optional[torch.Tensor] = None
+        self._probe_calls = 0      # host counter of forward calls, probed or not
+        self._recall_sums = None   # fp32 [2,B,H] on the device: recall and oracle recall, summed over the probed calls
+        self._recall_count = 0
+        if self.probe not in (None, "recall"):
+            raise ValueError(f"probe must be None or 'recall', got {self.probe!r}")
+        if self.probe == "recall":
+            if not 1 <= self.probe_samples <= ops.RECALL_MAX_SAMPLES:
+                raise ValueError(f"probe_samples must be in [1, {ops.RECALL_MAX_SAMPLES}], got {self.probe_samples}")
+            if self.probe_every < 1:
+                raise ValueError(f"probe_every must be >= 1, got {self.probe_every}")
+            video = int(cfg["width"]) * int(cfg["height"]) * int(cfg["depth"])
+            if self.probe_samples > video:
+                raise ValueError(f"probe_samples {self.probe_samples} exceeds the {video} video tokens")
+            # probe_samples distinct REORDERED positions of the video part (the reordered sequence is
+            # [video in Gilbert order, text]), drawn ONCE from a CPU generator, as the judge's rows are:
+            # a call consumes no random numbers and can be captured
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(self.probe_seed)
+            pos = torch.randperm(video, generator=gen)[:self.probe_samples]
+            self.register_buffer("probe_pos", pos.to(torch.int32), persistent=False)
         self.block = int(cfg.get("block", 128))
         self.num_keep = int(cfg.get("num_keep", 32))
         if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
@@ -348,6 +383,33 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self.last_head_sparsity, self.last_head_budget = sparsity, budget
         return budget
 
+    def _probe_recall(self, q, k, mask, rows):
+        """probe="recall": ops.mask_recall on this call's q, k and the mask its attention launch uses.
+        Three launches on the current stream; the results stay on the device."""
+        pos = self.probe_pos
+        if pos.device != q.device or pos.dtype != torch.int32:
+            pos = pos.to(device=q.device, dtype=torch.int32)
+            self.probe_pos = pos
+        with torch.no_grad():
+            rec, ora = ops.mask_recall(q.detach(), k.detach(), mask, pos, rows=rows)
+            if self._recall_sums is None or self._recall_sums.shape[1:] != rec.shape \
+                    or self._recall_sums.device != rec.device:
+                self._recall_sums = torch.zeros(2, *rec.shape, device=rec.device, dtype=torch.float32)
+                self._recall_count = 0
+            self._recall_sums[0].add_(rec)
+            self._recall_sums[1].add_(ora)
+        self._recall_count += 1
+        self.last_recall, self.last_oracle_recall = rec, ora
+
+    @property
+    def recall(self):
+        """(recall, oracle recall): fp32 [B,H] means over the probed calls, or None before the first.
+        Reading it synchronises once; the forward never does."""
+        if self._recall_sums is None or self._recall_count == 0:
+            return None
+        mean = (self._recall_sums / self._recall_count).cpu()
+        return mean[0], mean[1]
+
     def _mask_rule(self, B, H, nb, device, max_keep=None):
         """The ops.MaskRule of a call, or None when the options are the scalar energy rule's.
         ``max_keep``: the judge's int32 [B,H] counts, in place of max_retain_ratio's."""
@@ -463,6 +525,10 @@ class AdaptiveBlockSparseAttn(nn.Module):
             # head_mask_type's ones read literally: every head uses base_blockmask head 0 (a
             # head-stride-0 view; the kernels index the mask through its strides)
             mask = mask[:, :1].expand(B, H, mask.shape[2], mask.shape[3])
+        if self.probe == "recall":
+            if self._probe_calls % self.probe_every == 0:
+                self._probe_recall(q, k, mask, rows)
+            self._probe_calls += 1
         if not fused:
             from .autograd import adaptive_split_attention
             out = adaptive_split_attention(q, k, v, mask, rows, self.sample_gap,

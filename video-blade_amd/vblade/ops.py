@@ -790,6 +790,88 @@ def head_budget(sparsity, nb: int, base: float, clamp=(0.05, 0.9), variant: str 
     return (keep, ratio) if want_ratio else keep
 
 
+# ----------------------------------------------------------------------------------------------
+# attention-recall probe
+# ----------------------------------------------------------------------------------------------
+RECALL_MAX_SAMPLES = _lib.VB_RECALL_MAX_SAMPLES
+
+
+def recall_probe_pos(probe_pos, L: int, dev) -> torch.Tensor:
+    """The probe positions of mask_recall as a device int32 [S] tensor. A host-side ``probe_pos``
+    (list, tuple or numpy array) is range-checked against [0, L) here; a device tensor cannot be
+    checked without a synchronisation and is clamped to [0, L-1] by the kernel instead."""
+    if isinstance(probe_pos, torch.Tensor):
+        if probe_pos.dim() != 1:
+            raise ValueError(f"mask_recall: probe_pos must be one-dimensional, got {tuple(probe_pos.shape)}")
+        if probe_pos.is_cuda:
+            _check_dev("mask_recall: probe_pos", probe_pos, dev)
+            return probe_pos.to(torch.int32).contiguous()
+        probe_pos = probe_pos.numpy()
+    r = np.asarray(probe_pos)
+    if r.ndim != 1 or r.size == 0 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("mask_recall: probe_pos must be a non-empty one-dimensional list of integers")
+    if r.min() < 0 or r.max() >= L:
+        raise ValueError(f"mask_recall: probe_pos must lie in [0, {L}), got [{r.min()}, {r.max()}]")
+    return torch.from_numpy(r.astype(np.int32)).to(dev)
+
+
+def mask_recall(q, k, block_mask, probe_pos, *, rows=None, scale=None, want_rows: bool = False):
+    """vb_mask_recall: the exact softmax mass ``block_mask`` keeps for S <= 64 probe queries per head,
+    and the best mass a mask with as many blocks could have kept. q,k [B,H,L,D] (strided views are
+    read in place); block_mask [B,H,nb,nb] uint8 or bool in reordered order (a head-stride-0 view is
+    read as it is); ``probe_pos`` the REORDERED positions of the probe queries (a device int32
+    tensor, or a host list / numpy array, which is range-checked), shared by every (b,h); ``rows``
+    the reordered position -> caller row index the attention launch takes (None: identity). Returns
+    (recall, oracle_recall), fp32 [B,H]: the means over the probes; with ``want_rows`` also
+    (row_recall, row_oracle, row_kept), fp32 / fp32 / int32 [B,H,S]."""
+    if k.shape != q.shape or q.dim() != 4:
+        raise ValueError(f"mask_recall: q and k must share a [B,H,L,D] shape, got {tuple(q.shape)} "
+                         f"and {tuple(k.shape)}")
+    dev = _require_gpu(q, k, block_mask)
+    B, H, L, D = q.shape
+    nb = (L + BLOCK - 1) // BLOCK
+    if block_mask.dim() != 4 or block_mask.shape[0] != B or block_mask.shape[1] != H:
+        raise ValueError(f"mask_recall: block_mask must be [B,H,nb,nb] = [{B},{H},{nb},{nb}], "
+                         f"got {tuple(block_mask.shape)}")
+    if block_mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"mask_recall: block_mask must be uint8 or bool, got {block_mask.dtype}")
+    m = _mask_u8(block_mask, L, L)
+    probe_pos = recall_probe_pos(probe_pos, L, dev)
+    S = probe_pos.numel()
+    if not 1 <= S <= RECALL_MAX_SAMPLES:
+        raise ValueError(f"mask_recall: 1 to {RECALL_MAX_SAMPLES} probe positions, got {S}")
+    if rows is not None:
+        _check_dev("mask_recall: rows", rows, dev)
+        if rows.dtype != torch.int32 or rows.numel() != L:
+            raise ValueError(f"mask_recall: rows must be int32 [{L}], got {rows.dtype} {tuple(rows.shape)}")
+        rows = rows.contiguous()
+    a = _lib.RecallArgs()
+    a.B, a.H, a.L, a.D, a.S = B, H, L, D, S
+    a.scale = float(scale) if scale else 0.0
+    a.dtype = _dtype_code(q)
+    lib = _lib.load()
+    nbytes = int(lib.vb_mask_recall_workspace_size(ctypes.byref(a)))
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    q, k = _aligned_bhld(q), _aligned_bhld(k)
+    recall = torch.empty(B, H, device=dev, dtype=torch.float32)
+    oracle = torch.empty(B, H, device=dev, dtype=torch.float32)
+    row_recall = row_oracle = row_kept = None
+    if want_rows:
+        row_recall = torch.empty(B, H, S, device=dev, dtype=torch.float32)
+        row_oracle = torch.empty(B, H, S, device=dev, dtype=torch.float32)
+        row_kept = torch.empty(B, H, S, device=dev, dtype=torch.int32)
+    a.q, a.k = q.data_ptr(), k.data_ptr()
+    a.q_stride, a.k_stride = _s3(q), _s3(k)
+    a.rows, a.probe_pos = _ptr(rows), probe_pos.data_ptr()
+    a.block_mask = m.data_ptr()
+    a.mask_stride = (ctypes.c_int64 * 3)(m.stride(0), m.stride(1), m.stride(2))
+    a.recall, a.oracle_recall = recall.data_ptr(), oracle.data_ptr()
+    a.row_recall, a.row_oracle, a.row_kept = _ptr(row_recall), _ptr(row_oracle), _ptr(row_kept)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    check(lib.vb_mask_recall(ctypes.byref(a), _stream(dev)), "vb_mask_recall")
+    return (recall, oracle, row_recall, row_oracle, row_kept) if want_rows else (recall, oracle)
+
+
 def pool_kv_outputs(k, gap: int, reordered: bool = False):
     """Allocate pool_kv's outputs (kp, vp[, k_r, v_r]) on the current stream. A caller that launches
     pool_kv on a side stream allocates them BEFORE enqueueing other work whose temporaries could
