@@ -253,7 +253,9 @@ def test_gilbert_rearranger_round_trip_cpu():
 # The attention entries' argument validation and workspace arithmetic, pinned value by value. Every
 # case below is refused by a host check, so nothing is launched and the fake (non-null, 16-byte
 # aligned) pointers are never dereferenced. The literals were recorded from the library before the
-# backward's host layer moved into a unit of its own: a refactor of that layer must reproduce them.
+# backward's host layer moved into a unit of its own, and the forward entries' (vb_attn_fwd,
+# vb_ml_attn_fwd, vb_block_sparse_attn_fwd) before the forward's did: a refactor of either layer must
+# reproduce them.
 # ---------------------------------------------------------------------------------------------
 _PTR, _WS = 1 << 20, 1 << 24
 _B, _H, _L, _LK, _LKP, _GAP, _D = 1, 2, 200, 330, 42, 8, 64
@@ -326,6 +328,21 @@ def _bs_bwd_args():
     return a
 
 
+# vb_block_sparse_attn_fwd's positional arguments, by name
+_BSF_NAMES = ("q", "k", "v", "cu_q", "cu_k", "head_mask_type", "streaming_info", "mask", "batch", "num_heads",
+              "head_dim", "max_seqlen_q", "max_seqlen_k", "p_dropout", "deterministic", "softmax_scale",
+              "is_causal", "exact_streaming", "dtype", "out", "lse", "mask_head_mode", "stream")
+
+
+def _bs_fwd_args():
+    a = dict.fromkeys(_BSF_NAMES, None)
+    for n in ("q", "k", "v", "cu_q", "cu_k", "out", "lse"):
+        a[n] = _PTR
+    a.update(batch=_B, num_heads=_H, head_dim=_D, max_seqlen_q=_L, max_seqlen_k=_LK, p_dropout=0.0,
+             deterministic=1, softmax_scale=0.0, is_causal=0, exact_streaming=0, dtype=0, mask_head_mode=0)
+    return a
+
+
 def _set(**kw):
     def f(a):
         for k, v in kw.items():
@@ -383,6 +400,21 @@ _REJECTIONS = [
     ("vb_attn_fwd", "1025 blocks", _set(Lk=_TOO_LONG), _UNS, "vb_attn_fwd: Lk too long"),
     ("vb_attn_fwd", "pooled without vp", _set(vp=None), _INV, "vb_attn_fwd: pooled branch needs vp and Lkp > 0"),
     ("vb_attn_fwd", "D=96 and dtype 7", _set(D=96, dtype=7), _INV, "attn: unknown dtype"),
+    ("vb_attn_fwd", "B=0", _set(B=0), _INV, "vb_attn_fwd: B, H, Lq, D must be positive"),
+    ("vb_attn_fwd", "neither branch", _set(use_main=0, kp=None), _INV, "vb_attn_fwd: nothing to attend to"),
+    ("vb_attn_fwd", "q stride of 4", _set(q_stride=(4, 4, 4)), _INV,
+     "vb_attn_fwd: q/out strides must be multiples of 8 elements"),
+    ("vb_attn_fwd", "out stride of 4", _set(out_stride=(4, 4, 4)), _INV,
+     "vb_attn_fwd: q/out strides must be multiples of 8 elements"),
+    ("vb_attn_fwd", "pooled stride of 4", _set(vp_stride=(4, 4, 4)), _INV,
+     "vb_attn_fwd: kp/vp strides must be multiples of 8 elements"),
+    ("vb_attn_fwd", "pooled row stride 2^24", _row_stride("kp_stride", 1 << 23), _UNS,
+     "vb_attn_fwd: k/v/kp/vp row strides must be < 2^24 bytes"),
+    ("vb_attn_fwd", "stride of 4 and pointer off by 8", _set(k_stride=(4, 4, 4), k=_PTR + 8), _INV,
+     "vb_attn_fwd: k/v strides must be multiples of 8 elements"),
+    # reachable only without the main branch: with it, such an Lk is "too long" first
+    ("vb_attn_fwd", "kv_rows with Lk 2^24 pooled only", _set(use_main=0, kv_rows=_PTR, Lk=1 << 24), _UNS,
+     "vb_attn_fwd: kv_rows needs Lk < 2^24"),
 
     ("vb_ml_attn_fwd", "null tensor", _set(level_mask=None), _INV,
      "vb_ml_attn_fwd: missing q/kpyr/vpyr/level_mask/out"),
@@ -393,6 +425,25 @@ _REJECTIONS = [
     ("vb_ml_attn_fwd", "pointer off by 8", _set(kpyr=_PTR + 8), _INV,
      "vb_ml_attn_fwd: tensors must be 16-byte aligned"),
     ("vb_ml_attn_fwd", "1025 blocks", _set(L=_TOO_LONG), _UNS, "vb_ml_attn_fwd: L too long"),
+    ("vb_ml_attn_fwd", "L=0", _set(L=0), _INV, "vb_ml_attn_fwd: B, H, L must be positive"),
+    # head_dim before dtype here, the other way round in vb_attn_fwd: both orders are pinned
+    ("vb_ml_attn_fwd", "D=96 and dtype 7", _set(D=96, dtype=7), _UNS,
+     "vb_ml_attn_fwd: head_dim must be 64 or 128, got 96"),
+
+    ("vb_block_sparse_attn_fwd", "p_dropout=0.1", _set(p_dropout=0.1), _UNS,
+     "vb_block_sparse_attn_fwd: p_dropout must be 0"),
+    ("vb_block_sparse_attn_fwd", "is_causal=1", _set(is_causal=1), _UNS,
+     "vb_block_sparse_attn_fwd: causal/streaming not supported"),
+    ("vb_block_sparse_attn_fwd", "mask_head_mode=7", _set(mask_head_mode=7), _INV,
+     "vb_block_sparse_attn_fwd: unknown mask_head_mode"),
+    ("vb_block_sparse_attn_fwd", "null tensor", _set(cu_k=None), _INV, "vb_block_sparse_attn_fwd: null tensor"),
+    ("vb_block_sparse_attn_fwd", "batch=0", _set(batch=0), _INV, "vb_block_sparse_attn_fwd: bad sizes"),
+    ("vb_block_sparse_attn_fwd", "1025 blocks", _set(max_seqlen_k=_TOO_LONG), _UNS,
+     "vb_block_sparse_attn_fwd: max_seqlen_k too long"),
+    ("vb_block_sparse_attn_fwd", "D=96", _set(head_dim=96), _UNS, "attn: head_dim must be 64 or 128, got 96"),
+    ("vb_block_sparse_attn_fwd", "dtype 7", _set(dtype=7), _INV, "attn: unknown dtype"),
+    ("vb_block_sparse_attn_fwd", "k slice >= 2 GiB", _set(num_heads=1 << 16), _UNS,
+     "vb_block_sparse_attn_fwd: a sequence's k/v span >= 2 GiB"),
 
     ("vb_attn_bwd", "null tensor", _set(dv=None), _INV, "vb_attn_bwd: missing tensor"),
     ("vb_attn_bwd", "D=96", _set(D=96), _UNS, "vb_attn_bwd: head_dim must be 64 or 128, got 96"),
@@ -465,12 +516,14 @@ _REJECTIONS = [
      "vb_ml_attn_bwd: workspace missing or smaller than vb_ml_attn_bwd_workspace_size()"),
 ]
 _VALID = {"vb_attn_fwd": _fwd_args, "vb_ml_attn_fwd": _ml_fwd_args, "vb_attn_bwd": _bwd_args,
-          "vb_block_sparse_attn_bwd": _bs_bwd_args, "vb_ml_attn_bwd": _ml_bwd_args}
+          "vb_block_sparse_attn_fwd": _bs_fwd_args, "vb_block_sparse_attn_bwd": _bs_bwd_args,
+          "vb_ml_attn_bwd": _ml_bwd_args}
+_POSITIONAL = {"vb_block_sparse_attn_fwd": _BSF_NAMES, "vb_block_sparse_attn_bwd": _BS_NAMES}
 
 
 def _call(lib, entry, a):
     if isinstance(a, dict):
-        return getattr(lib, entry)(*(a[n] for n in _BS_NAMES))
+        return getattr(lib, entry)(*(a[n] for n in _POSITIONAL[entry]))
     return getattr(lib, entry)(ctypes.byref(a), None)
 
 
@@ -483,6 +536,15 @@ def test_attention_entries_reject_one_fault_at_a_time(lib, entry, fault, mutate,
     got = lib.vb_last_error().decode()
     print(f"{entry} [{fault}]: {rc} {got!r}")
     assert (rc, got) == (code, message)
+
+
+def test_forward_entries_reject_null_args(lib):
+    """A NULL args struct is refused by the first check of either struct-taking forward entry."""
+    for entry in ("vb_attn_fwd", "vb_ml_attn_fwd"):
+        rc = getattr(lib, entry)(None, None)
+        got = lib.vb_last_error().decode()
+        print(f"{entry} [null args]: {rc} {got!r}")
+        assert (rc, got) == (_INV, f"{entry}: null args")
 
 
 # vb_attn_bwd_workspace_size at B=1, H=2: (Lq, Lk, D, q_rows, pooled) -> bytes; pooled Lkp = ceil(Lk / 8)

@@ -5,9 +5,9 @@
 // 293-324, 106-109) and fuses the pooled-KV branch + LSE combine (:367-393) into the same softmax.
 //
 // Geometry: one 256-thread workgroup (4 waves) per (b, h, 128-row q-block); each wave owns 32
-// query rows. Keys stream through LDS in 64-key tiles (two per kept 128-key mask block, then the
-// pooled keys), double-buffered: the next tile's global loads are issued before the current
-// tile's MFMAs and written to the other LDS buffer after them (one barrier per tile).
+// query rows. Keys stream through an LDS ring of 64-key tiles (two per kept 128-key mask block,
+// then the pooled keys): 2 slots at D=128, 3 at D=64, filled by LDS-DMA (global_load_lds_dwordx4)
+// one or two tiles ahead of the tile being read, one barrier per tile.
 //
 // Per wave and tile:
 //   S^T (64 keys x 32 q) = K . Q^T       v_mfma_f32_32x32x16: A = K rows (ds_read_b128 of an
@@ -19,7 +19,13 @@
 //                                        the S^T accumulator registers (no LDS round trip)
 // Gilbert reorder: q/k/v rows are gathered through q_rows / kv_rows and O/LSE scattered through
 // q_rows, so the reference's index_select + cat + reverse (:141-161) cost no pass of their own.
-#include <cstdlib>
+//
+// Layout: the work-item decode and the build constants (namespace fwd) are in vb_attn_fwd.hpp, the
+// entry points and their validation in vb_attn_fwd_host.cpp. Here the kept-block list builder and
+// the register-only softmax helpers are free functions; attn_fwd_item holds what indexes the LDS ring,
+// under the headings "how a tile's source is chosen", "how a tile is issued", "one tile, inference",
+// "one tile, training" and "epilogue". Every piece that is still inline there changed some kernel's
+// instructions when it was moved out (forward layout).
 #include <type_traits>
 
 #include "vb_args.hpp"
@@ -43,29 +49,11 @@ namespace vb {
 #ifndef VB_LAZY_COUNT
 #define VB_LAZY_COUNT 0   // diagnostic builds: count lazy-max slow paths (g_vb_stamp[10]) per tile half ([11])
 #endif
-#ifndef VB_LAZY_NOCHECK
-#define VB_LAZY_NOCHECK 0   // diagnostic builds only: no overflow check (timing of the fast path alone)
-#endif
-#ifndef VB_NODMA
-#define VB_NODMA 0   // diagnostic: tiles past the first ring fill are not loaded (stale LDS)
-#endif
-#if VB_DIAG || VB_LAZY_COUNT
+#if VB_LAZY_COUNT
 __device__ unsigned long long g_vb_stamp[16];
-#endif
-#if VB_DIAG
-// diagnostic-only cycle stamps (never in the product build): per-segment sums of s_memtime
-__device__ __forceinline__ unsigned long long vb_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define VB_STAMP(var) const unsigned long long var = vb_stamp()
-#define VB_ACC(i, d) acc_st[i] += (d)
+#define VB_LAZY_ADD(slot, n) if (lane == 0) atomicAdd(&g_vb_stamp[slot], n)
 #else
-#define VB_STAMP(var)
-#define VB_ACC(i, d)
+#define VB_LAZY_ADD(slot, n)
 #endif
 
 // LDS of one attention workgroup: the K/V ring, the kept-block list and its count, and (gathered
@@ -73,6 +61,76 @@ __device__ __forceinline__ unsigned long long vb_stamp() {
 template <int D, bool kKvRows>
 constexpr int fwd_smem_bytes() {
   return ((D == 64) ? 3 : 2) * 2 * kKT * D * 2 + kMaxBlocks * 2 + 16 + (kKvRows ? 4 * 512 : 0);
+}
+
+// ---- which key blocks a q-block keeps (wave 0; list / list_n in LDS) ---------------------------------
+// position of this lane's set bit among the set bits of a wave ballot
+__device__ __forceinline__ int ballot_rank(unsigned long long bal) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+}
+// the kept key blocks of mask row `mrow` (all nbk if dense; none without the main branch), ascending
+__device__ __forceinline__ void build_kept_list(const uint8_t* mrow, bool dense, bool use_main, int nbk, int qblk,
+                                                int lane, uint16_t* list, int* list_n) {
+  int n = 0;
+  int dpos = -1;   // list position of the diagonal block (key block qblk), if kept
+  if (use_main) {
+    for (int j0 = 0; j0 < nbk; j0 += 64) {
+      const int j = j0 + lane;
+      const bool keep = (j < nbk) && (dense || mrow[j] != 0);
+      const unsigned long long bal = __ballot(keep);
+      if (keep) {
+        const int pos = n + ballot_rank(bal);
+        list[pos] = (uint16_t)j;
+        if (j == qblk) dpos = pos;
+      }
+      n += __popcll(bal);
+    }
+    // Diagonal block first: in the Gilbert order a q-block's own key block usually holds its
+    // largest scores, so the running max is set once on the first tile (fewer rescales; the
+    // lazy-max launches rarely leave their fast path). Placement only: same sum, other order.
+    // The last key block keeps its place (a half-empty tail tile must stay the last tile).
+    const unsigned long long db = __ballot(dpos > 0);
+    if (db != 0 && qblk != nbk - 1) {
+      const int dp = __builtin_amdgcn_readlane(dpos, (int)__builtin_ctzll(db));
+      if (lane == 0) {
+        const uint16_t t = list[0];
+        list[0] = (uint16_t)qblk;
+        list[dp] = t;
+      }
+    }
+  }
+  if (lane == 0) *list_n = n;
+}
+
+// ---- softmax helpers on one 32-key half of S^T (this lane's 16 values; registers only) --------------
+// row max: 7 v_max3 + 1 v_max
+__device__ __forceinline__ float half_max(const f32x16& x) {
+  const float a = max3f(max3f(max3f(x[0], x[1], x[2]), x[3], x[4]), x[5], x[6]);
+  const float c = max3f(max3f(max3f(x[8], x[9], x[10]), x[11], x[12]), x[13], x[14]);
+  return max3f(a, c, fmaxf(x[7], x[15]));
+}
+// P = exp2(S) packed to the storage type (the PV operands of k-steps 2kt, 2kt+1) WITHOUT
+// overwriting S; returns the lane's fp32 sum (four independent chains)
+template <class T, int kPrio>
+__device__ __forceinline__ float exp_pack(const f32x16& x, typename T::vec8& p0, typename T::vec8& p1) {
+  float e[16];
+  float h4[4];
+  if constexpr (kPrio & 4) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    e[r] = exp2_fast(x[r]);
+    h4[r & 3] = r < 4 ? e[r] : h4[r & 3] + e[r];   // chains start at their first value (no 0 + e)
+  }
+  u32x4 u0, u1;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    u0[w] = pack2<T>(e[2 * w], e[2 * w + 1]);
+    u1[w] = pack2<T>(e[8 + 2 * w], e[8 + 2 * w + 1]);
+  }
+  p0 = __builtin_bit_cast(typename T::vec8, u0);
+  p1 = __builtin_bit_cast(typename T::vec8, u1);
+  if constexpr (kPrio & 4) __builtin_amdgcn_s_setprio(0);
+  return (h4[0] + h4[1]) + (h4[2] + h4[3]);
 }
 
 // Persistent dispatch (vb_attn_args.work_queue; vb_common.hpp): the launch is resident-sized and
@@ -85,21 +143,22 @@ constexpr int fwd_smem_bytes() {
 // One work item: the (b, h, 128-row q-block) of virtual blockIdx `vblk`. With a work queue, lane 0
 // of wave 0 claims the workgroup's next item after the tile loop (`next`), so the claim's round
 // trip overlaps the epilogue.
+// kCBias selects the tile body. true = inference launches (no LSE output): the S accumulator starts
+// at (bias - m) instead of 0 and Q is pre-scaled by scale*log2(e), so every score leaves the MFMA as
+// the exp2 argument itself (no per-score v_fma before the v_exp: the D=64 loop is VALU-issue-bound),
+// and the running max is lazy ("one tile, inference"). The extra rounding of q*scale to 16 bits stays
+// within the stated tolerance. false = launches that return the LSE for a backward: they keep the
+// unscaled Q, so forward and backward see the same scores, and take every tile's row max ("one tile,
+// training").
 template <int D, class T, bool kPool, bool kKvRows, bool kML, bool kCBias, bool kWQ>
 __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk, int& next) {
   constexpr int KS = D / 16;                   // k-steps of the QK^T product
   constexpr int DT = D / 32;                   // 32-wide d tiles of the output
-  constexpr bool kSplitPV = VB_FWD_SPLIT_PV && D == 64;   // measured: +0.8 % at D=64, -1.4 % at D=128
-  // kCBias (inference launches: no LSE output): the S accumulator starts at (bias - m) instead of 0
-  // and Q is pre-scaled by scale*log2(e), so every score leaves the MFMA as the exp2 argument itself:
-  // no per-score v_fma before the v_exp (the D=64 loop is VALU-issue-bound). The extra rounding of
-  // q*scale to 16 bits stays within the stated tolerance; launches that return the LSE for a
-  // backward keep the unscaled Q so forward and backward see the same scores.
-  constexpr bool kLazy = kCBias && VB_FWD_LAZY && !VB_MFMA_ROWSUM && !VB_DIAG;
-  // s_setprio around the MFMA chains of the lazy (inference) loop: with two waves per SIMD (D=128)
-  // the wave in its MFMA phase keeps the matrix pipe fed while the other runs its softmax VALU
-  // (Wan +4 %); the LSE-returning loop and the 3-wave D=64 kernel measured slower with it
-  constexpr int kPrio = !kLazy ? 0 : D == 64 ? VB_FWD_PRIO64 : VB_FWD_PRIO128;
+  constexpr bool kSplitPV = fwd::split_pv(D);
+  // s_setprio around the MFMA chains of the inference loop: with two waves per SIMD (D=128) the wave
+  // in its MFMA phase keeps the matrix pipe fed while the other runs its softmax VALU (Wan +4 %);
+  // the LSE-returning loop and the 3-wave D=64 kernel measured slower with it
+  constexpr int kPrio = !kCBias ? 0 : D == 64 ? fwd::kPrio64 : fwd::kPrio128;
   constexpr float kLazyBound = std::is_same<T, BF16>::value ? kLazyBoundBF16 : kLazyBoundF16;
   constexpr int kRowB = D * 2;                 // bytes per key row
   constexpr int kMatBytes = kKT * kRowB;       // one 64-key K (or V) tile
@@ -133,28 +192,9 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
   const int half = lane >> 5;
   const int l32 = lane & 31;
 
-  // Work order (placement only affects speed, never results). Workgroups are dealt round-robin
-  // over the 8 XCDs (blockIdx % 8 share one XCD and its 4 MiB L2).
-  //  phase 1: the `heavy_rows` last q-block rows of every head (CogVideoX's dense text rows, the
-  //           longest workgroups) go first, spread over all XCDs;
-  //  phase 2: every XCD takes a contiguous, head-major range of the remaining (head, q-block)
-  //           work, so the pooled K/V and the kept K/V blocks of the one or two heads an XCD is
-  //           working on are re-read from its own L2 instead of the Infinity Cache / HBM.
   VB_ATRACE_START(0);
-  const int BH = p.B * p.H;
-  const int hr = min(p.heavy_rows, p.nbq);
-  const int n_heavy = hr * BH;
   int qblk, bh;
-  if (vblk < n_heavy) {
-    qblk = p.nbq - 1 - vblk / BH;
-    bh = vblk % BH;
-  } else {
-    const int rows_left = p.nbq - hr;
-    int lin = xcd_linear(vblk - n_heavy, rows_left * BH);
-    if (p.q_order) lin = __builtin_amdgcn_readfirstlane(p.q_order[lin]);   // longest first (attn_order_kernel)
-    bh = lin / rows_left;
-    qblk = rows_left - 1 - lin % rows_left;
-  }
+  fwd_item_decode(p, vblk, bh, qblk);
   const int b = bh / p.H, h = bh % p.H;
 
   int Lq = p.Lq, Lk = p.Lk;
@@ -182,7 +222,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
   }
   if (kML) {
     // multi-level: per-level lists of key blocks (levels 1, 2, 4, 8, in that order), built in two
-    // passes over the mask row (counts, then positions) so they share the one kMaxBlocks array
+    // passes over the mask row (counts, then positions) so they share the one kMaxBlocks array.
     if (tid < 64) {
       int cnt[4] = {0, 0, 0, 0};
       for (int j0 = 0; j0 < nbk; j0 += 64) {
@@ -207,36 +247,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
       if (lane < 4) list_n[lane] = cnt[0] * (lane == 0) + cnt[1] * (lane == 1) + cnt[2] * (lane == 2) + cnt[3] * (lane == 3);
     }
   } else if (tid < 64) {
-    int n = 0;
-    int dpos = -1;   // list position of the diagonal block (key block qblk), if kept
-    if (p.use_main) {
-      for (int j0 = 0; j0 < nbk; j0 += 64) {
-        const int j = j0 + lane;
-        const bool keep = (j < nbk) && (dense || mrow[j] != 0);
-        const unsigned long long bal = __ballot(keep);
-        if (keep) {
-          const int pos = n + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-          list[pos] = (uint16_t)j;
-          if (j == qblk) dpos = pos;
-        }
-        n += __popcll(bal);
-      }
-      // Diagonal block first: in the Gilbert order a q-block's own key block usually holds its
-      // largest scores, so the running max is set once on the first tile (fewer rescales; the
-      // lazy-max launches rarely leave their fast path). Placement only: same sum, other order.
-      // The last key block keeps its place (a half-empty tail tile must stay the last tile).
-      const unsigned long long db = __ballot(dpos > 0);
-      if (db != 0 && qblk != nbk - 1) {
-        const int dp = __builtin_amdgcn_readlane(dpos, (int)__builtin_ctzll(db));
-        if (lane == 0) {
-          const uint16_t t = list[0];
-          list[0] = (uint16_t)qblk;
-          list[dp] = t;
-        }
-      }
-    }
-    if (lane == 0) *list_n = n;
+    build_kept_list(mrow, dense, p.use_main, nbk, qblk, lane, list, list_n);
   }
 
   // ---- Q fragment (B operand of S^T = K.Q^T): row l32 of this wave, d = 16s + 8*half + j --------
@@ -267,7 +278,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
   // kQLate: the Q fragment is loaded after the ring's first DMAs are issued (below), so its round
   // trip and theirs overlap; only the q_rows entry (issued above) and the mask row precede the
   // barrier. Otherwise Q is loaded first and retired before the DMA ring starts.
-  constexpr bool kQLate = D == 64 ? VB_FWD_QLATE64 : (kLazy && !kKvRows) ? VB_FWD_QLATE128_LAZY : VB_FWD_QLATE128;
+  constexpr bool kQLate = D == 64 ? fwd::kQLate64 : (kCBias && !kKvRows) ? fwd::kQLate128Lazy : fwd::kQLate128;
   if constexpr (kQLate) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave 0's list writes
     __builtin_amdgcn_s_barrier();                           // kept-block list visible
@@ -302,6 +313,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     vpbase = reinterpret_cast<const uint8_t*>(p.vp) + 2 * (b * p.vps[0] + h * p.vps[1]);
   }
 
+  // ---- how a tile's source is chosen --------------------------------------------------------------
   // where tile t's keys come from; `blk_raw` = list[t >> 1] (read ahead by the caller)
   auto tile_src = [&](int t, int blk_raw) __attribute__((always_inline)) -> TileSrc {
     TileSrc s;
@@ -365,11 +377,12 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     return (int)list[e0] | ((int)list[e1] << 16);
   };
 
+  // ---- how a tile is issued -------------------------------------------------------------------------
   // Tile t -> LDS ring slot t % kBufs by LDS-DMA (global_load_lds_dwordx4, 1 KiB per
   // wave-instruction, written linearly). The images' XOR swizzles (k_off / v_off_bytes) are
   // applied to each lane's SOURCE chunk instead: LDS slot `sl` of row r holds the chunk that
-  // k_off / v_off_bytes would have placed there. Waves 0-1 (D=64) fill K, waves 2-3 fill V.
-  // every wave fills ONE matrix: waves 0-1 -> K, waves 2-3 -> V (kInstPerWave*2 == kInstPerMat)
+  // k_off / v_off_bytes would have placed there. Every wave fills ONE matrix: waves 0-1 -> K,
+  // waves 2-3 -> V (kInstPerWave*2 == kInstPerMat).
   static_assert(2 * kInstPerWave == kInstPerMat, "DMA split assumes two waves per matrix");
   const int my_mat = wave >> 1;
   const uint8_t* my_base = my_mat == 0 ? kbase : vbase;
@@ -414,13 +427,15 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     my_rc[i] = my_chunk[i] * 16;
     if constexpr (kML) my_voff[i] = (my_row[i] & 15) * my_rowb + my_chunk[i] * 16;
   }
+  // Persistent launches (kWQ) issue every K/V DMA through dma16_unscoped: the DMAs stay invisible to
+  // hipcc's LDS-DMA waits across the item loop (persistent dispatch)
   auto ml_issue = [&](const MlTileSrc src, int slot) __attribute__((always_inline)) {
     uint8_t* dst = smem + slot * kBufBytes + my_mat * kMatBytes + (wave & 1) * kInstPerWave * 1024;
     const int soffA = __builtin_amdgcn_readfirstlane(src.srcA * my_rowb);
     const int soffB = __builtin_amdgcn_readfirstlane(src.srcB * my_rowb);
 #pragma unroll
     for (int i = 0; i < kInstPerWave; ++i)
-      if constexpr (kWQ && VB_FWD_DMA_UNSCOPED) dma16_unscoped(my_rsrc, dst + i * 1024, my_voff[i], (i * kRowsPerInst >= 16) ? soffB : soffA);
+      if constexpr (kWQ) dma16_unscoped(my_rsrc, dst + i * 1024, my_voff[i], (i * kRowsPerInst >= 16) ? soffB : soffA);
       else dma16(my_rsrc, dst + i * 1024, my_voff[i], (i * kRowsPerInst >= 16) ? soffB : soffA);
   };
   // Gathered K/V rows (kv_rows: reordered key -> caller row; the module's path on the caller's own
@@ -441,7 +456,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     }
     if (lane < 32) {
       uint8_t* dst = ibase + (t & 3) * 512;
-      if constexpr (kWQ && VB_FWD_DMA_UNSCOPED) {   // as dma16_unscoped
+      if constexpr (kWQ) {   // as dma16_unscoped
         uint32_t a = __builtin_amdgcn_readfirstlane(
             static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*)dst)));
         asm("" : "+s"(a));
@@ -456,7 +471,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     uint8_t* dst = smem + slot * kBufBytes + my_mat * kMatBytes + (wave & 1) * kInstPerWave * 1024;
     // this wave's i-th 1 KiB piece of the tile
     auto piece = [&](int i, srd_t sd, int voff, int soff) __attribute__((always_inline)) {
-      if constexpr (kWQ && VB_FWD_DMA_UNSCOPED) dma16_unscoped(sd, dst + i * 1024, voff, soff);
+      if constexpr (kWQ) dma16_unscoped(sd, dst + i * 1024, voff, soff);
       else dma16(sd, dst + i * 1024, voff, soff);
     };
     const bool pooled = kPool && src.pooled;
@@ -496,36 +511,24 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     }
   };
 
+  // ---- running state of this lane's query row -------------------------------------------------------
   f32x16 o[DT];
 #pragma unroll
   for (int i = 0; i < DT; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-  float m = kCBias ? 0.f : -INFINITY;  // running max (exp2 domain) of this lane's query row
+  float m = kCBias ? 0.f : -INFINITY;  // running max (exp2 domain)
   float l = 0.f;        // running partial row sum (this half's keys)
-  // kCBias: cb = cur_bias - m in every register (the first QK^T MFMA's C operand); `first` forces
-  // the first tile to set m from its own maximum
+  // inference only: cb = cur_bias - m in every register (the first QK^T MFMA's C operand); `first`
+  // makes the first tile set m from its own maximum
   f32x16 cb;
 #pragma unroll
   for (int r = 0; r < 16; ++r) cb[r] = 0.f;
   int cur_bias_bits = 0;   // bit pattern of the bias folded into cb (0.0f)
   bool first = true;
-#if VB_MFMA_ROWSUM
-  // Row sums on the matrix core (D=64 is VALU-bound): lsum += ones . P^T, every register of the
-  // accumulator = the lane's full row sum of the bf16 P that also feeds O (no VALU adds).
-  f32x16 lsum;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) lsum[r] = 0.f;
-  typename T::vec8 ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = T::from_f32(1.0f);
-#endif
 
   const int vrow = 4 * half + (lane & 15) / 4;
   const int vcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-#if VB_DIAG
-  unsigned long long acc_st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
 
   // Loop-invariant per-lane LDS addresses: the images' XOR swizzles depend only on the lane's own
   // row bits (K: row l32 [+32 kt]; V: row vrow [+16 k + 8]), so every K/V fragment read of every
@@ -548,20 +551,9 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
     const uint8_t* kl = smem + kSlot * kBufBytes;
     const float bias = __int_as_float(bias_bits);
     f32x16 s[2];
-    if constexpr (kCBias) {
-      // wave-uniform; only where the tile source changes (pooled, levels). Compared as bit patterns
-      // in SGPRs (a scalar compare; a float compare would run on the VALU every tile)
-      if (bias_bits != cur_bias_bits) {
-        asm volatile("");
-        const float db = bias - __int_as_float(cur_bias_bits);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cb[r] += db;
-        cur_bias_bits = bias_bits;
-      }
-    }
     // V^T fragments (ds_read_b64_tr_b16) for the first VPRE k-steps, issued before the softmax
     // VALU so they land while it runs; the rest are fetched one k-step ahead inside the PV loop.
-    constexpr int VPRE = (D == 64 && !VB_MFMA_ROWSUM) ? (kKvRows ? VB_VPRE64_ROWS : VB_VPRE64) : 2;
+    constexpr int VPRE = D == 64 ? (kKvRows ? fwd::kVPre64Rows : fwd::kVPre64) : 2;
     s16x4 vlo[4][DT], vhi[4][DT];
     auto read_v = [&](int kk) __attribute__((always_inline)) {
       const int row0 = (kk >> 1) * 32 + 16 * (kk & 1);   // + vrow (in v_lane)
@@ -576,98 +568,80 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
       for (int dt = 0; dt < DT; ++dt)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vlo[kk][dt]), "+v"(vhi[kk][dt]));
     };
+    // k-step kk (16 keys) of O^T += V^T . P^T: its V^T fragments have landed and those VPRE k-steps
+    // ahead are fetched (next_v), then its MFMAs on the packed P (pv)
+    auto next_v = [&](int kk) __attribute__((always_inline)) {
+      wait_v(kk);
+      if (kk + VPRE < 4) read_v(kk + VPRE);
+    };
+    auto pv = [&](int kk, const typename T::vec8& pf) __attribute__((always_inline)) {
+      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) o[dt] = T::mfma32(join8<T>(vlo[kk][dt], vhi[kk][dt]), pf, o[dt]);
+      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(0);
+    };
+    // keys of half kt at or past klen -> -inf (tail tiles)
     auto mask_tail = [&](int kt) __attribute__((always_inline)) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half >= klen) s[kt][r] = -INFINITY;
     };
-    // row max of one 32-key half (this lane's 16 values): 7 v_max3 + 1 v_max
-    auto half_max = [&](const f32x16& x) __attribute__((always_inline)) -> float {
-      const float a = max3f(max3f(max3f(x[0], x[1], x[2]), x[3], x[4]), x[5], x[6]);
-      const float c = max3f(max3f(max3f(x[8], x[9], x[10]), x[11], x[12]), x[13], x[14]);
-      return max3f(a, c, fmaxf(x[7], x[15]));
-    };
-    auto compute_s = [&]() __attribute__((always_inline)) {
+    // S^T = seed + K.Q^T of both halves
+    auto scores = [&](const f32x16& seed) __attribute__((always_inline)) {
       if constexpr (kPrio & 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         typename T::vec8 kf[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) kf[ks] = lds_b128<T>(kl + kt * 32 * kRowB, k_lane[ks]);
-        if constexpr (kCBias) {
-          s[kt] = T::mfma32(kf[0], qf[0], cb);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
-          s[kt] = T::mfma32(kf[0], qf[0], s[kt]);
-        }
+        s[kt] = T::mfma32(kf[0], qf[0], seed);
 #pragma unroll
         for (int ks = 1; ks < KS; ++ks) s[kt] = T::mfma32(kf[ks], qf[ks], s[kt]);
       }
       if constexpr (kPrio & 1) __builtin_amdgcn_s_setprio(0);
     };
-    // P = exp2(S) of one half packed to the storage type (the PV operands of k-steps 2kt, 2kt+1)
-    // WITHOUT overwriting S; returns the lane's fp32 sum (four independent chains)
-    auto exp_pack = [&](const f32x16& x, typename T::vec8& p0, typename T::vec8& p1) __attribute__((always_inline)) -> float {
-      float e[16];
-      float h4[4];
-      if constexpr (kPrio & 4) __builtin_amdgcn_s_setprio(1);
+
+    // ---- one tile, inference (kCBias): lazy running max ---------------------------------------------
+    // The first tile takes its exact row max; after that no per-tile max is computed: P = exp2(S - m)
+    // uses the standing m, and the row sum of each half-tile (>= each of its P) is checked against
+    // kLazyBound. A passing check bounds every P, and so O and l, far from overflow. P is packed into
+    // separate registers, so S survives the exp: a failing check (rare, wave-uniform) raises m to the
+    // rows' max of that S, rescales O and l, and redoes the exp. m never exceeds the true running
+    // max, so l >= 1 after the first tile, and P's bf16 rounding is relative: the result equals the
+    // exact-max form up to rounding.
+    if constexpr (kCBias) {
+      // wave-uniform; only where the tile source changes (pooled, levels). Compared as bit patterns
+      // in SGPRs (a scalar compare; a float compare would run on the VALU every tile)
+      if (bias_bits != cur_bias_bits) {
+        asm volatile("");
+        const float db = bias - __int_as_float(cur_bias_bits);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        e[r] = exp2_fast(x[r]);
-        h4[r & 3] = r < 4 ? e[r] : h4[r & 3] + e[r];   // chains start at their first value (no 0 + e)
+        for (int r = 0; r < 16; ++r) cb[r] += db;
+        cur_bias_bits = bias_bits;
       }
-      u32x4 u0, u1;
+      // raise m by the rows' max mt of S (if > 0), rescaling O, l, the C seed and the S halves >= kt0
+      // (a half whose P is already in O is dead: touching it would keep it live)
+      auto raise_m = [&](float mt, auto KT0) __attribute__((always_inline)) {
+        constexpr int kt0 = decltype(KT0)::value;
+        const float delta = fmaxf(max_xor32(mt), 0.f);
+        const float alpha = exp2_fast(-delta);
+        m += delta;
+        l *= alpha;
 #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        u0[w] = pack2<T>(e[2 * w], e[2 * w + 1]);
-        u1[w] = pack2<T>(e[8 + 2 * w], e[8 + 2 * w + 1]);
-      }
-      p0 = __builtin_bit_cast(typename T::vec8, u0);
-      p1 = __builtin_bit_cast(typename T::vec8, u1);
-      if constexpr (kPrio & 4) __builtin_amdgcn_s_setprio(0);
-      return (h4[0] + h4[1]) + (h4[2] + h4[3]);
-    };
-    auto pv_pk = [&](int kk, const typename T::vec8& pf) __attribute__((always_inline)) {
-      wait_v(kk);
-      if (kk + VPRE < 4) read_v(kk + VPRE);
-      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(1);
+        for (int i = 0; i < DT; ++i)
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) o[dt] = T::mfma32(join8<T>(vlo[kk][dt], vhi[kk][dt]), pf, o[dt]);
-      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(0);
-    };
-    // raise m by the rows' max mt of S (if > 0), rescaling O, l, the C seed and the S halves >= kt0
-    // (a half whose P is already in O is dead: touching it would keep it live)
-    auto raise_m = [&](float mt, auto KT0) __attribute__((always_inline)) {
-      constexpr int kt0 = decltype(KT0)::value;
-      const float delta = fmaxf(max_xor32(mt), 0.f);
-      const float alpha = exp2_fast(-delta);
-      m += delta;
-      l *= alpha;
+          for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
 #pragma unroll
-      for (int i = 0; i < DT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        cb[r] -= delta;
-        if (kt0 == 0) s[0][r] -= delta;
-        s[1][r] -= delta;
-      }
-    };
-    if constexpr (kLazy) {
-      // Lazy running max (inference launches). The first tile takes its exact row max; after that
-      // no per-tile max is computed: P = exp2(S - m) uses the standing m, and the row sum of each
-      // half-tile (>= each of its P) is checked against kLazyBound. A passing check bounds every P,
-      // and so O and l, far from overflow. P is packed into separate registers, so S survives the
-      // exp: a failing check (rare, wave-uniform) raises m to the rows' max of that S, rescales O
-      // and l, and redoes the exp. m never exceeds the true running max, so l >= 1 after the first
-      // tile, and P's bf16 rounding is relative: the result equals the exact-max form up to
-      // rounding.
-      compute_s();
+        for (int r = 0; r < 16; ++r) {
+          cb[r] -= delta;
+          if (kt0 == 0) s[0][r] -= delta;
+          s[1][r] -= delta;
+        }
+      };
+      scores(cb);
 #pragma unroll
       for (int kk = 0; kk < VPRE; ++kk) read_v(kk);
-      if (klen < kKT) {
+      if (klen < kKT) {   // tail tile only; the volatile asm keeps it a real (wave-uniform) branch
         asm volatile("");
         mask_tail(0);
         mask_tail(1);
@@ -688,141 +662,123 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
       if constexpr (kSplitPV) {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
-          float hs = exp_pack(s[kt], pf[2 * kt], pf[2 * kt + 1]);
-          if (!VB_LAZY_NOCHECK && !__all(hs <= kLazyBound)) {
+          float hs = exp_pack<T, kPrio>(s[kt], pf[2 * kt], pf[2 * kt + 1]);
+          if (!__all(hs <= kLazyBound)) {
             asm volatile("");
-#if VB_LAZY_COUNT
-            if (lane == 0) atomicAdd(&g_vb_stamp[10], 1ull);
-#endif
+            VB_LAZY_ADD(10, 1ull);
             // O and l already hold the first half's P when kt = 1: they are rescaled with the rest
             if (kt == 0) raise_m(half_max(s[0]), std::integral_constant<int, 0>{});
             else raise_m(half_max(s[1]), std::integral_constant<int, 1>{});
-            hs = exp_pack(s[kt], pf[2 * kt], pf[2 * kt + 1]);
+            hs = exp_pack<T, kPrio>(s[kt], pf[2 * kt], pf[2 * kt + 1]);
           }
           l += hs;
-          pv_pk(2 * kt, pf[2 * kt]);
-          pv_pk(2 * kt + 1, pf[2 * kt + 1]);
+#pragma unroll
+          for (int kk = 2 * kt; kk < 2 * kt + 2; ++kk) {
+            next_v(kk);
+            pv(kk, pf[kk]);
+          }
         }
       } else {
-        float h0 = exp_pack(s[0], pf[0], pf[1]);
-        float h1 = exp_pack(s[1], pf[2], pf[3]);
-        if (!VB_LAZY_NOCHECK && !__all(fmaxf(h0, h1) <= kLazyBound)) {
+        float h0 = exp_pack<T, kPrio>(s[0], pf[0], pf[1]);
+        float h1 = exp_pack<T, kPrio>(s[1], pf[2], pf[3]);
+        if (!__all(fmaxf(h0, h1) <= kLazyBound)) {
           asm volatile("");
-#if VB_LAZY_COUNT
-          if (lane == 0) atomicAdd(&g_vb_stamp[10], 1ull);
-#endif
+          VB_LAZY_ADD(10, 1ull);
           raise_m(fmaxf(half_max(s[0]), half_max(s[1])), std::integral_constant<int, 0>{});
-          h0 = exp_pack(s[0], pf[0], pf[1]);
-          h1 = exp_pack(s[1], pf[2], pf[3]);
+          h0 = exp_pack<T, kPrio>(s[0], pf[0], pf[1]);
+          h1 = exp_pack<T, kPrio>(s[1], pf[2], pf[3]);
         }
         l += h0 + h1;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) pv_pk(kk, pf[kk]);
+        for (int kk = 0; kk < 4; ++kk) {
+          next_v(kk);
+          pv(kk, pf[kk]);
+        }
       }
-#if VB_LAZY_COUNT
-      if (lane == 0) atomicAdd(&g_vb_stamp[11], kSplitPV ? 2ull : 1ull);
-#endif
-      return;
+      VB_LAZY_ADD(11, kSplitPV ? 2ull : 1ull);
     }
-    compute_s();
+
+    // ---- one tile, training (!kCBias: the launch returns the LSE): every tile's row max -------------
+    // S holds the raw scores (unscaled Q, accumulator from 0); P = exp2(S * c + bias - m).
+    if constexpr (!kCBias) {
+      f32x16 zero;
 #pragma unroll
-    for (int kk = 0; kk < VPRE; ++kk) read_v(kk);
-    VB_STAMP(s1);
-    if (klen < kKT) {   // tail tile only; the volatile asm keeps it a real (wave-uniform) branch
-      asm volatile("");
+      for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+      scores(zero);
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half >= klen) s[kt][r] = -INFINITY;
-    }
-    // row max: four independent chains (short dependency chains, max3-friendly)
-    float mq[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {   // 16 v_max3 for 32 values (the minimum), depth 6
-      const f32x16& x = s[c >> 1];
-      const int o = 8 * (c & 1);
-      mq[c] = max3f(max3f(max3f(x[o], x[o + 1], x[o + 2]), x[o + 3], x[o + 4]), x[o + 5], x[o + 6]);
-    }
-    const float f1 = max3f(mq[0], mq[1], s[0][7]);
-    const float f2 = max3f(mq[2], mq[3], s[0][15]);
-    float mt = max3f(max3f(f1, f2, s[1][7]), s[1][15], s[1][15]);
-    if constexpr (kCBias) mt = max_xor32(mt);  // tile row max relative to m (bias included)
-    else mt = max_xor32(mt) * p.c + bias;       // tile row max, exp2 domain
-    // Deferred rescale (guide T13): the running max m is raised only when some row's tile max
-    // exceeds it by more than kRescaleSlack (log2 units), so P = exp2(s - m) <= 2^kRescaleSlack.
-    // O and l always share the same m, so the result is exact up to rounding; without the slack
-    // nearly every tile of a 32-row wave rescales (some row's max grows), a 40-VALU O-wide pass.
-    // The empty volatile asm keeps hipcc from if-converting this block into every iteration.
-    if (kCBias) {
-      if (first || !__all(mt <= kRescaleSlack)) {
+      for (int kk = 0; kk < VPRE; ++kk) read_v(kk);
+      if (klen < kKT) {   // tail tile, as above; written out (through mask_tail the listing changes)
         asm volatile("");
-        // first tile: m := the tile's max (O and l are still zero; alpha would be meaningless)
-        const float delta = first ? mt : fmaxf(mt, 0.f);
-        const float alpha = first ? 0.f : exp2_fast(-delta);
-        m += delta;
-        l *= alpha;
-#if VB_MFMA_ROWSUM
 #pragma unroll
-        for (int r = 0; r < 16; ++r) lsum[r] *= alpha;
-#endif
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half >= klen) s[kt][r] = -INFINITY;
+      }
+      // row max: four independent chains (short dependency chains, max3-friendly)
+      float mq[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {   // 16 v_max3 for 32 values (the minimum), depth 6
+        const f32x16& x = s[c >> 1];
+        const int o = 8 * (c & 1);
+        mq[c] = max3f(max3f(max3f(x[o], x[o + 1], x[o + 2]), x[o + 3], x[o + 4]), x[o + 5], x[o + 6]);
+      }
+      const float f1 = max3f(mq[0], mq[1], s[0][7]);
+      const float f2 = max3f(mq[2], mq[3], s[0][15]);
+      float mt = max3f(max3f(f1, f2, s[1][7]), s[1][15], s[1][15]);
+      mt = max_xor32(mt) * p.c + bias;       // tile row max, exp2 domain
+      // Deferred rescale (guide T13): the running max m is raised only when some row's tile max
+      // exceeds it by more than kRescaleSlack (log2 units), so P = exp2(s - m) <= 2^kRescaleSlack.
+      // O and l always share the same m, so the result is exact up to rounding; without the slack
+      // nearly every tile of a 32-row wave rescales (some row's max grows), a 40-VALU O-wide pass.
+      // The empty volatile asm keeps hipcc from if-converting this block into every iteration.
+      if (!__all(mt <= m + fwd::kRescaleSlack)) {
+        asm volatile("");
+        const float mn = fmaxf(m, mt);
+        const float alpha = exp2_fast(m - mn);
+        m = mn;
+        l *= alpha;
 #pragma unroll
         for (int i = 0; i < DT; ++i)
 #pragma unroll
           for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
+      }
+      const float nbias = bias - m;
+      float lq[4] = {0.f, 0.f, 0.f, 0.f};   // four independent partial sums
+      if constexpr (kSplitPV) {
+        // exp of the first 32 keys, their P.V k-steps, then the second 32: the PV MFMAs of the first
+        // half overlap the second half's exp VALU (same sums, same order: bit-identical results)
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float e = exp2_fast(fmaf(s[kt][r], p.c, nbias));
+            s[kt][r] = e;
+            lq[(2 * kt + r) & 3] = (kt == 0 && r < 4) ? e : lq[(2 * kt + r) & 3] + e;   // no 0 + e
+          }
+#pragma unroll
+          for (int kk = 2 * kt; kk < 2 * kt + 2; ++kk) {
+            wait_v(kk);
+            if (kk + VPRE < 4) read_v(kk + VPRE);
+            const typename T::vec8 pf = pack8<T>(s[kk >> 1], 8 * (kk & 1));
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) o[dt] = T::mfma32(join8<T>(vlo[kk][dt], vhi[kk][dt]), pf, o[dt]);
+          }
+        }
+        l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
+      } else {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s[kt][r] -= delta;
+          for (int r = 0; r < 16; ++r) {
+            const float e = exp2_fast(fmaf(s[kt][r], p.c, nbias));
+            s[kt][r] = e;
+            lq[(2 * kt + r) & 3] = (kt == 0 && r < 4) ? e : lq[(2 * kt + r) & 3] + e;
+          }
+        l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
+        // O^T += V^T . P^T : 4 k-steps of 16 keys
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cb[r] -= delta;
-        first = false;
-      }
-    } else if (!__all(mt <= m + kRescaleSlack)) {
-      asm volatile("");
-      const float mn = fmaxf(m, mt);
-      const float alpha = exp2_fast(m - mn);
-      m = mn;
-      l *= alpha;
-#if VB_MFMA_ROWSUM
-#pragma unroll
-      for (int r = 0; r < 16; ++r) lsum[r] *= alpha;
-#endif
-#pragma unroll
-      for (int i = 0; i < DT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-    }
-    const float nbias = bias - m;
-    float ls = 0.f;
-    if (VB_DIAG && (p.dbg & 1)) {   // diagnostic: no exp
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = kCBias ? s[kt][r] : fmaf(s[kt][r], p.c, nbias);
-          s[kt][r] = e;
-          ls += e;
-        }
-    } else if (VB_MFMA_ROWSUM) {
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[kt][r] = exp2_fast(kCBias ? s[kt][r] : fmaf(s[kt][r], p.c, nbias));
-    } else if (kSplitPV) {
-      // exp of the first 32 keys, their P.V k-steps, then the second 32: the PV MFMAs of the first
-      // half overlap the second half's exp VALU (same sums, same order: bit-identical results)
-      float lq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = exp2_fast(kCBias ? s[kt][r] : fmaf(s[kt][r], p.c, nbias));
-          s[kt][r] = e;
-          lq[(2 * kt + r) & 3] = (kt == 0 && r < 4) ? e : lq[(2 * kt + r) & 3] + e;   // no 0 + e
-        }
-#pragma unroll
-        for (int kk = 2 * kt; kk < 2 * kt + 2; ++kk) {
+        for (int kk = 0; kk < 4; ++kk) {
           wait_v(kk);
           if (kk + VPRE < 4) read_v(kk + VPRE);
           const typename T::vec8 pf = pack8<T>(s[kk >> 1], 8 * (kk & 1));
@@ -830,39 +786,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
           for (int dt = 0; dt < DT; ++dt) o[dt] = T::mfma32(join8<T>(vlo[kk][dt], vhi[kk][dt]), pf, o[dt]);
         }
       }
-      ls = (lq[0] + lq[1]) + (lq[2] + lq[3]);
-    } else {
-      float lq[4] = {0.f, 0.f, 0.f, 0.f};   // four independent partial sums
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = exp2_fast(kCBias ? s[kt][r] : fmaf(s[kt][r], p.c, nbias));
-          s[kt][r] = e;
-          lq[(2 * kt + r) & 3] = (kt == 0 && r < 4) ? e : lq[(2 * kt + r) & 3] + e;
-        }
-      ls = (lq[0] + lq[1]) + (lq[2] + lq[3]);
     }
-    l += ls;
-    VB_STAMP(s2);
-    VB_ACC(3, s2 - s1);
-    // O^T += V^T . P^T : 4 k-steps of 16 keys (done above in the split form)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      if (kSplitPV && !(VB_DIAG && (p.dbg & 1)) && !VB_MFMA_ROWSUM) break;
-      wait_v(kk);
-      if (kk + VPRE < 4) read_v(kk + VPRE);
-      const typename T::vec8 pf = pack8<T>(s[kk >> 1], 8 * (kk & 1));
-      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) o[dt] = T::mfma32(join8<T>(vlo[kk][dt], vhi[kk][dt]), pf, o[dt]);
-      if constexpr (kPrio & 2) __builtin_amdgcn_s_setprio(0);
-#if VB_MFMA_ROWSUM
-      lsum = T::mfma32(ones, pf, lsum);
-#endif
-    }
-    VB_STAMP(s3);
-    VB_ACC(4, s3 - s2);
   };
 
   // Each ring slot remembers its tile's source (SGPRs, written when the tile is issued), and the
@@ -919,7 +843,6 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
   auto body = [&](int t, auto U) __attribute__((always_inline)) {
     constexpr int u = decltype(U)::value;
     constexpr int un = (u + kBufs - 1) % kBufs;   // slot of the tile issued during this one
-    VB_STAMP(st0);
     // retire this wave's DMAs of tile t (younger tiles stay in flight); the barrier then makes
     // every wave's part visible and proves slot (t-1) % kBufs is no longer being read
     const int ti = t + kBufs - 1;
@@ -945,14 +868,10 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
       __builtin_amdgcn_s_barrier();
       if (ti < ntiles) {
         slot_src[un] = any_tile_src(ti, next_blk);
-        if (!(VB_NODMA && ti >= kBufs)) any_issue(slot_src[un], un);   // VB_NODMA: timing diagnostic only
+        any_issue(slot_src[un], un);
         next_blk = any_list_at(ti + 1);   // in flight during this tile's compute
       }
     }
-    VB_STAMP(st1);
-    VB_ACC(0, st1 - st0);
-    VB_STAMP(st2);
-    VB_ACC(1, st2 - st1);
     const Src src = slot_src[u];
     int bias_bits;
     if constexpr (kML) {   // + ln(p) in the exp2 domain: log2(p) in {0, 1, 2, 3}
@@ -961,10 +880,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
       bias_bits = (kPool && src.pooled) ? pool_bias_bits : 0;
     }
     bias_bits = __builtin_amdgcn_readfirstlane(bias_bits);
-    if (VB_DIAG && (p.dbg & 2)) return;   // diagnostic: stream tiles only
     tile_step(U, bias_bits, src.klen);
-    VB_STAMP(st3);
-    VB_ACC(2, st3 - st2);
   };
   for (int t0 = 0; t0 < ntiles; t0 += kBufs) {
     body(t0, std::integral_constant<int, 0>{});
@@ -981,19 +897,9 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
   // stores, so its round trip overlaps them. Not inside the loop: the claim's wait for its own
   // result (and the waits hipcc then places after the branch) would drain the DMA ring every round.
   if (kWQ && tid == 0) next = wq_fetch(p.work_queue, blockIdx.x & 7, p.n_items);
-#if VB_DIAG
-  if (lane == 0) {
-    for (int i = 0; i < 5; ++i) atomicAdd(&g_vb_stamp[i], acc_st[i]);
-    atomicAdd(&g_vb_stamp[8], (unsigned long long)ntiles);
-  }
-#endif
 
-  // ---- epilogue -----------------------------------------------------------------------------------
-#if VB_MFMA_ROWSUM
-  const float lt = lsum[0];
-#else
+  // ---- epilogue: O / l in the storage type to the caller's row, and the row's LSE ------------------
   const float lt = add_xor32(l);
-#endif
   const float inv = (lt > 0.f) ? 1.0f / lt : 0.f;
   // streaming heads (unsupported) are flagged with NaN outputs written as bit patterns: this
   // translation unit is compiled with -fno-honor-nans, so no float arithmetic may produce them
@@ -1032,7 +938,7 @@ __device__ __forceinline__ void attn_fwd_item(const FwdParams& p, const int vblk
 }
 
 template <int D, class T, bool kPool, bool kKvRows, bool kML = false, bool kCBias = false, bool kPersist = false>
-__global__ void __launch_bounds__(kThreads, (D == 64 ? VB_FWD_WAVES_D64 : 2)) attn_fwd_kernel(const FwdParams p) {
+__global__ void __launch_bounds__(kThreads, (D == 64 ? fwd::kWavesD64 : 2)) attn_fwd_kernel(const FwdParams p) {
   if constexpr (!kPersist) {   // one workgroup per item
     int next;
     attn_fwd_item<D, T, kPool, kKvRows, kML, kCBias, false>(p, blockIdx.x, next);
@@ -1070,6 +976,7 @@ __global__ void __launch_bounds__(1024) attn_order_kernel(const FwdParams p, int
   const int BH = p.B * p.H;
   const int hr = min(p.heavy_rows, p.nbq);
   const int rows_left = p.nbq - hr;
+  // XCD x's range of the linear index: the inverse of xcd_linear (vb_tiles.hpp), whose slot 0 is `start`
   const int nwg = rows_left * BH;
   const int x = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7;
@@ -1092,7 +999,8 @@ __global__ void __launch_bounds__(1024) attn_order_kernel(const FwdParams p, int
   for (int i = threadIdx.x; i < nbins; i += blockDim.x) bins[i] = 0;
   __syncthreads();
   auto key_of = [&](int lin) -> int {
-    const int bh = lin / rows_left, qblk = rows_left - 1 - lin % rows_left;
+    int bh, qblk;
+    fwd_phase2_item(lin, rows_left, bh, qblk);
     bool nan_head = false;
     const uint8_t* mh = head_mask_base(p.mask, p.ms, p.head_mask_type, p.H, bh / p.H, bh % p.H, nan_head, p.hm_mode);
     int kept = p.nbk;
@@ -1139,11 +1047,11 @@ __global__ void __launch_bounds__(1024) attn_order_kernel(const FwdParams p, int
   }
 }
 
-// Grid of one launch: one workgroup per item, or (work queue) as many as are resident at once —
-// the occupancy of this instantiation times the device's CUs (host queries, cached per kernel and
-// device; no device synchronisation), a multiple of 8 so every XCD gets the same number.
+// ---- launchers (declared in vb_attn_fwd.hpp; here because resident_grid needs the kernel symbol) ---
 // Grid of one launch: one workgroup per item, or (persistent instantiation, with a work queue) as
-// many as are resident at once (resident_grid: occupancy x CUs, a multiple of 8).
+// many as are resident at once — the occupancy of that instantiation times the device's CUs (host
+// queries, cached per kernel and device; no device synchronisation), a multiple of 8 so every XCD
+// gets the same number.
 template <auto Kern, auto KernP>
 static int launch_one(FwdParams p, hipStream_t stream, const char* what) {
   const unsigned items = (unsigned)(p.nbq * p.B * p.H);
@@ -1164,18 +1072,27 @@ static int launch_attn(const FwdParams& p, hipStream_t stream, const char* what)
                     attn_fwd_kernel<D, T, kPool, kKvRows, kML, kCBias, true>>(p, stream, what);
 }
 
-static int dispatch_fwd(const FwdParams& p, int D, int dtype, bool pool, hipStream_t stream) {
-  if (!dtype_ok(dtype)) return fail(VB_ERR_INVALID, "attn: unknown dtype");
-  if (!head_dim_ok(D)) return fail(VB_ERR_UNSUPPORTED, "attn: head_dim must be 64 or 128, got " + std::to_string(D));
-  const bool cbias = VB_FWD_CBIAS && p.lse == nullptr;
+// inference launches (no LSE output) take the kCBias kernel
+int launch_fwd(const FwdParams& p, int D, int dtype, bool pool, hipStream_t stream) {
   return dispatch_head(D, dtype, [&](auto d, auto t, auto pl, auto rows, auto cb) {
     return launch_attn<d(), decltype(t), pl(), rows(), false, cb()>(p, stream, "attn_fwd_kernel");
-  }, pool, p.kv_rows != nullptr, cbias);
+  }, pool, p.kv_rows != nullptr, p.lse == nullptr);
+}
+
+int launch_ml_fwd(const FwdParams& p, int D, int dtype, hipStream_t stream) {
+  return dispatch_head(D, dtype, [&](auto d, auto t, auto cb) {
+    return launch_attn<d(), decltype(t), false, false, true, cb()>(p, stream, "attn_fwd_kernel (multi-level)");
+  }, p.lse == nullptr);
+}
+
+int launch_attn_order(const FwdParams& p, int32_t* order, hipStream_t stream) {
+  hipLaunchKernelGGL(attn_order_kernel, dim3(8), dim3(1024), 0, stream, p, order);
+  return check_launch("attn_order_kernel");
 }
 
 }  // namespace vb
 
-#if VB_DIAG || VB_LAZY_COUNT
+#if VB_LAZY_COUNT
 extern "C" int vb_diag_stamps(unsigned long long* host16, int reset) {
   (void)hipDeviceSynchronize();
   (void)hipMemcpyFromSymbol(host16, HIP_SYMBOL(vb::g_vb_stamp), sizeof(unsigned long long) * 16);
@@ -1187,162 +1104,6 @@ extern "C" int vb_diag_stamps(unsigned long long* host16, int reset) {
 }
 #endif
 
-extern "C" int vb_attn_fwd(const vb_attn_args* a, void* stream) {
-  using namespace vb;
-  if (!a) return fail(VB_ERR_INVALID, "vb_attn_fwd: null args");
-  if (a->B <= 0 || a->H <= 0 || a->Lq <= 0 || a->D <= 0)
-    return fail(VB_ERR_INVALID, "vb_attn_fwd: B, H, Lq, D must be positive");
-  if (!a->q || !a->out || (a->use_main && (!a->k || !a->v || a->Lk <= 0)))
-    return fail(VB_ERR_INVALID, "vb_attn_fwd: missing q/k/v/out");
-  const bool pool = a->kp != nullptr;
-  if (!a->use_main && !pool) return fail(VB_ERR_INVALID, "vb_attn_fwd: nothing to attend to");
-  if (pool && (!a->vp || a->Lkp <= 0)) return fail(VB_ERR_INVALID, "vb_attn_fwd: pooled branch needs vp and Lkp > 0");
-  const int nbq = (a->Lq + kQBlk - 1) / kQBlk;
-  const int nbk = a->use_main ? (a->Lk + kQBlk - 1) / kQBlk : 0;
-  if (nbk > kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: Lk too long");
-  for (int i = 0; i < 3; ++i) {
-    if ((a->q_stride[i] | a->out_stride[i]) & 7) return fail(VB_ERR_INVALID, "vb_attn_fwd: q/out strides must be multiples of 8 elements");
-    if (a->use_main && ((a->k_stride[i] | a->v_stride[i]) & 7)) return fail(VB_ERR_INVALID, "vb_attn_fwd: k/v strides must be multiples of 8 elements");
-    if (pool && ((a->kp_stride[i] | a->vp_stride[i]) & 7)) return fail(VB_ERR_INVALID, "vb_attn_fwd: kp/vp strides must be multiples of 8 elements");
-  }
-  if (a->kv_rows && a->Lk >= (1 << 24))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: kv_rows needs Lk < 2^24");
-  // the tile DMA offsets use 24-bit multiplies: row strides below 2^24 bytes (16 MiB per row)
-  if ((a->use_main && (a->k_stride[2] * 2 >= (1 << 24) || a->v_stride[2] * 2 >= (1 << 24))) ||
-      (pool && (a->kp_stride[2] * 2 >= (1 << 24) || a->vp_stride[2] * 2 >= (1 << 24))))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: k/v/kp/vp row strides must be < 2^24 bytes");
-  if (a->use_main && (!slice_fits32(a->Lk, a->k_stride[2], a->D) || !slice_fits32(a->Lk, a->v_stride[2], a->D)))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: a k/v (b,h) slice spans >= 2 GiB");
-  if (pool && (!slice_fits32(a->Lkp, a->kp_stride[2], a->D) || !slice_fits32(a->Lkp, a->vp_stride[2], a->D)))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_fwd: a kp/vp (b,h) slice spans >= 2 GiB");
-  if (!aligned16(a->q) || !aligned16(a->out) || (a->use_main && (!aligned16(a->k) || !aligned16(a->v))) ||
-      (pool && (!aligned16(a->kp) || !aligned16(a->vp))))
-    return fail(VB_ERR_INVALID, "vb_attn_fwd: tensors must be 16-byte aligned");
-  FwdParams p{};
-  p.q = a->q; p.k = a->k; p.v = a->v;
-  for (int i = 0; i < 3; ++i) {
-    p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i];
-    p.ms[i] = a->mask_stride[i]; p.kps[i] = a->kp_stride[i]; p.vps[i] = a->vp_stride[i];
-    p.os[i] = a->out_stride[i];
-  }
-  p.q_rows = a->q_rows; p.kv_rows = a->kv_rows;
-  p.use_main = a->use_main;
-  p.mask = a->block_mask;
-  p.kp = a->kp; p.vp = a->vp; p.Lkp = a->Lkp;
-  p.pool_bias_l2 = a->kp_log_bias * kLog2e;
-  p.out = a->out; p.lse = a->lse;
-  p.lse_s[0] = (int64_t)a->H * a->Lq; p.lse_s[1] = a->Lq;
-  p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->use_main ? a->Lk : 1; p.nbq = nbq; p.nbk = nbk;
-  p.c = scale_or_default(a->scale, a->D) * kLog2e;
-  p.heavy_rows = a->heavy_rows;
-#if VB_DIAG
-  if (const char* d = getenv("VB_DEBUG_ATTN")) p.dbg = atoi(d);
-#endif
-  p.q_len = a->q_lengths;
-  p.order_window = a->order_window;
-  p.work_queue = a->work_queue;
-  if (a->q_order && p.use_main && p.mask) {   // longest-first dispatch order (scheduling only)
-    hipLaunchKernelGGL(attn_order_kernel, dim3(8), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), p,
-                       a->q_order);
-    if (int rc = check_launch("attn_order_kernel")) return rc;
-    p.q_order = a->q_order;
-  }
-  return dispatch_fwd(p, a->D, a->dtype, pool, reinterpret_cast<hipStream_t>(stream));
-}
-
 #if VB_ATTN_TRACE
 VB_TRACE_GETTER(vb_debug_attn_trace, vb::g_attn_trace)
 #endif
-
-extern "C" int vb_kv_pyramid_rows(int L) {
-  const int lpad = (L + vb::kQBlk - 1) / vb::kQBlk * vb::kQBlk;
-  return 15 * (lpad / 8);
-}
-
-extern "C" int vb_ml_attn_fwd(const vb_ml_attn_args* a, void* stream) {
-  using namespace vb;
-  if (!a) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: null args");
-  if (a->B <= 0 || a->H <= 0 || a->L <= 0) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: B, H, L must be positive");
-  if (!a->q || !a->kpyr || !a->vpyr || !a->level_mask || !a->out)
-    return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: missing q/kpyr/vpyr/level_mask/out");
-  if (!head_dim_ok(a->D))
-    return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_fwd: head_dim must be 64 or 128, got " + std::to_string(a->D));
-  const int nb = (a->L + kQBlk - 1) / kQBlk;
-  if (nb > kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_fwd: L too long");
-  for (int i = 0; i < 3; ++i)
-    if ((a->q_stride[i] | a->out_stride[i]) & 7) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: q/out strides must be multiples of 8 elements");
-  const int R = vb_kv_pyramid_rows(a->L);
-  if ((int64_t)R * 2 * a->D >= (int64_t(1) << 31)) return fail(VB_ERR_UNSUPPORTED, "vb_ml_attn_fwd: a pyramid (b,h) slice spans >= 2 GiB");
-  if (!aligned16(a->q) || !aligned16(a->out) || !aligned16(a->kpyr) || !aligned16(a->vpyr))
-    return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: tensors must be 16-byte aligned");
-  FwdParams p{};
-  p.q = a->q; p.k = a->kpyr; p.v = a->vpyr;
-  for (int i = 0; i < 3; ++i) {
-    p.qs[i] = a->q_stride[i]; p.os[i] = a->out_stride[i]; p.ms[i] = a->mask_stride[i];
-  }
-  p.ks[0] = p.vs[0] = (int64_t)a->H * R * a->D;
-  p.ks[1] = p.vs[1] = (int64_t)R * a->D;
-  p.ks[2] = p.vs[2] = a->D;
-  p.q_rows = a->q_rows;
-  p.use_main = 1;
-  p.mask = a->level_mask;
-  p.out = a->out; p.lse = a->lse;
-  p.lse_s[0] = (int64_t)a->H * a->L; p.lse_s[1] = a->L;
-  p.B = a->B; p.H = a->H; p.Lq = a->L; p.Lk = a->L; p.nbq = nb; p.nbk = nb;
-  p.Lpad = nb * kQBlk;
-  p.ref_tail = a->ref_tail ? 1 : 0;
-  p.c = scale_or_default(a->scale, a->D) * kLog2e;
-  p.heavy_rows = a->heavy_rows;
-  p.work_queue = a->work_queue;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool cb = VB_FWD_CBIAS && p.lse == nullptr;   // inference launches (see kCBias)
-  if (!dtype_ok(a->dtype)) return fail(VB_ERR_INVALID, "vb_ml_attn_fwd: unknown dtype");
-  return dispatch_head(a->D, a->dtype, [&](auto d, auto t, auto cbias) {
-    return launch_attn<d(), decltype(t), false, false, true, cbias()>(p, st, "attn_fwd_kernel (multi-level)");
-  }, cb);
-}
-
-extern "C" int vb_block_sparse_attn_fwd(const void* q_unpad, const void* k_unpad, const void* v_unpad,
-                                        const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
-                                        const int32_t* head_mask_type, const int32_t* streaming_info,
-                                        const uint8_t* base_blockmask, int batch, int num_heads, int head_dim,
-                                        int max_seqlen_q, int max_seqlen_k, float p_dropout, int deterministic,
-                                        float softmax_scale, int is_causal, int exact_streaming, int dtype,
-                                        void* out_unpad, float* softmax_lse, int mask_head_mode, void* stream) {
-  using namespace vb;
-  (void)streaming_info;
-  (void)deterministic;
-  if (p_dropout != 0.f) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: p_dropout must be 0");
-  if (is_causal || exact_streaming) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: causal/streaming not supported");
-  if (mask_head_mode != VB_MASK_HEAD_PER_HEAD && mask_head_mode != VB_MASK_HEAD_SHARED0)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_fwd: unknown mask_head_mode");
-  if (!q_unpad || !k_unpad || !v_unpad || !cu_seqlens_q || !cu_seqlens_k || !out_unpad)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_fwd: null tensor");
-  if (batch <= 0 || num_heads <= 0 || max_seqlen_q <= 0 || max_seqlen_k <= 0)
-    return fail(VB_ERR_INVALID, "vb_block_sparse_attn_fwd: bad sizes");
-  const int nbq = (max_seqlen_q + kQBlk - 1) / kQBlk;
-  const int nbk = (max_seqlen_k + kQBlk - 1) / kQBlk;
-  if (nbk > kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: max_seqlen_k too long");
-  if (!slice_fits32(max_seqlen_k, (int64_t)num_heads * head_dim, head_dim))
-    return fail(VB_ERR_UNSUPPORTED, "vb_block_sparse_attn_fwd: a sequence's k/v span >= 2 GiB");
-  FwdParams p{};
-  p.q = q_unpad; p.k = k_unpad; p.v = v_unpad;
-  const int64_t row = (int64_t)num_heads * head_dim;
-  p.qs[0] = p.ks[0] = p.vs[0] = p.os[0] = 0;
-  p.qs[1] = p.ks[1] = p.vs[1] = p.os[1] = head_dim;
-  p.qs[2] = p.ks[2] = p.vs[2] = p.os[2] = row;
-  p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k;
-  p.head_mask_type = head_mask_type;
-  p.hm_mode = mask_head_mode;
-  p.use_main = 1;
-  p.mask = base_blockmask;  // may be NULL: dense
-  // base_blockmask [batch, n_sparse, nbq, nbk]: n_sparse (= number of heads whose mask id is 1) is
-  // counted on the device from head_mask_type (no host read of device memory, no sync).
-  p.ms[0] = head_mask_type ? -1 : (int64_t)num_heads * nbq * nbk;
-  p.ms[1] = (int64_t)nbq * nbk; p.ms[2] = nbk;
-  p.out = out_unpad; p.lse = softmax_lse;
-  p.lse_s[0] = (int64_t)num_heads * max_seqlen_q; p.lse_s[1] = max_seqlen_q;
-  p.B = batch; p.H = num_heads; p.Lq = max_seqlen_q; p.Lk = max_seqlen_k; p.nbq = nbq; p.nbk = nbk;
-  p.c = scale_or_default(softmax_scale, head_dim) * kLog2e;
-  return dispatch_fwd(p, head_dim, dtype, false, reinterpret_cast<hipStream_t>(stream));
-}

@@ -87,10 +87,7 @@ __device__ __forceinline__ float add_xor32(float x) {
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // ---------------------------------------------------------------- HBM passes beside the predictor
-#ifndef VB_POOL_WGS_DEFAULT
-#define VB_POOL_WGS_DEFAULT 0
-#endif
-constexpr int kPoolWgsDefault = VB_POOL_WGS_DEFAULT;
+constexpr int kPoolWgsDefault = 0;   // pool_grid's cap on workgroups; 0 = one per 256 chunks
 unsigned pool_grid(int64_t work_items);   // vb_pool.hip
 
 // ---------------------------------------------------------------- persistent work queues (ABI 4)

@@ -16,7 +16,7 @@ __global__ void __launch_bounds__(256) pool_kv_kernel(const PoolTask t) {
 
 // Workgroups of an HBM-bound pass that runs beside the predictor's score kernel on another stream:
 // a capped, grid-strided launch leaves most CUs to the MFMA-bound kernel instead of flooding the
-// dispatcher (the build's VB_POOL_WGS_DEFAULT; 0 = one workgroup per 256 chunks).
+// dispatcher (kPoolWgsDefault; 0 = one workgroup per 256 chunks).
 unsigned pool_grid(int64_t work_items) {
   constexpr int cap = kPoolWgsDefault;
   const int64_t n = (work_items + 255) / 256;

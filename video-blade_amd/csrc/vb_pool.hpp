@@ -19,38 +19,24 @@ struct PoolTask {
 
 // Work items idx0, idx0 + step, ...: one 16-byte chunk of one pooled row each. Every reordered row
 // is read by exactly one item, which also writes it to the copies. The gap rows are read in groups
-// of VB_POOL_GROUP with every load of a group issued before any is used; the fp32 sums keep the
+// of kPoolGroup with every load of a group issued before any is used; the fp32 sums keep the
 // sequential row order. The pass is HBM-latency bound with few workgroups, so a thread's steps
 // (item, group) are pipelined: the `rows` entries of step s+1 are loaded while step s's K/V rows are
 // in flight, into the other of two entry sets (the loop is unrolled by two, so no register copy of
 // a pending load forces a wait). Round 5: the entries had been loaded one per row, each behind a
 // vmcnt(0) that also waited for the previous rows, so a 15-row item took ~16 round trips.
-#ifndef VB_POOL_GROUP
-#define VB_POOL_GROUP 8
-#endif
-#ifndef VB_POOL_NT
-// 1: the K/V reads non-temporal (each row is read once; the score workgroups beside the pass keep
-// more of their L2), 2: the copies' stores too. Per CogVideoX call against the pipelined pass with
-// plain loads: 1.017/1.018x vs 1.015/1.012x, 2: 1.008x (profiles/archive/r05_pool_pipeline_ab.log)
-#define VB_POOL_NT 1
-#endif
+constexpr int kPoolGroup = 8;
+// The K/V reads are non-temporal (each row is read once; the score workgroups beside the pass keep
+// more of their L2), the copies' stores plain. Per CogVideoX call against the pipelined pass with
+// plain loads: 1.017/1.018x vs 1.015/1.012x; with non-temporal stores too 1.008x
+// (profiles/archive/r05_pool_pipeline_ab.log)
 __device__ __forceinline__ u32x4 pool_ld(const uint8_t* p) {
-#if VB_POOL_NT >= 1
   return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#else
-  return *reinterpret_cast<const u32x4*>(p);
-#endif
 }
-__device__ __forceinline__ void pool_st(uint8_t* p, const u32x4& x) {
-#if VB_POOL_NT >= 2
-  __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(p));
-#else
-  *reinterpret_cast<u32x4*>(p) = x;
-#endif
-}
+__device__ __forceinline__ void pool_st(uint8_t* p, const u32x4& x) { *reinterpret_cast<u32x4*>(p) = x; }
 template <class T, bool kRows>
 __device__ __forceinline__ void pool_kv_steps(const PoolTask& t, int64_t idx0, int64_t step) {
-  constexpr int G = VB_POOL_GROUP;
+  constexpr int G = kPoolGroup;
   const int CH = t.D / 8;
   const int64_t total = (int64_t)t.B * t.H * t.Lp * CH;
   if (idx0 >= total) return;
