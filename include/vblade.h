@@ -685,6 +685,64 @@ typedef struct vb_recall_args {
 uint64_t vb_mask_recall_workspace_size(const vb_recall_args* args);
 int vb_mask_recall(const vb_recall_args* args, void* stream);
 
+/* ==========================================================================================
+ * Mask predictor, second block score: the sampled softmax MASS of a (q-block, key-block) pair, beside
+ * the max proxy of vb_mask_predict (the largest single-key probability ratio of the block). The
+ * sampling, the mask rule (vb_block_mask_rule on `po`) and everything downstream are the existing
+ * ones; only the score differs. Additive to ABI 4.
+ *
+ * Sampled streams: those of vb_mask_predict. Per (b,h), block i < nb = ceil(L/128) and t < num_keep
+ * the reordered position is g = min(128*i + off[b,h,t], L-1) (the clamp is the replicate pad) and the
+ * caller's row is rows[g] (rows NULL: the identity). q_off gives the sampled queries qs, k_off the
+ * sampled keys ks, nb*num_keep rows each; row i*num_keep + t belongs to block i. The kernel clamps
+ * each offset to [0, 127] and each row number to [0, L-1] before it is used as an address.
+ *
+ * All arithmetic fp32 unless stated. For sampled query r and sampled key c of one (b,h):
+ *   s[r,c]    = <qs_r, ks_c> (MFMA, fp32 accumulation) * qk_scale;
+ *               qk_scale = fp32(scale) * fp32(1.44269504) as vb_mask_predict forms it, scale <= 0 ->
+ *               D^-1/2
+ *   M_r       = max_c s[r,c] (the rounded product of the largest dot product: qk_scale > 0);
+ *               l_r = sum_c exp2(s[r,c] - M_r), every s - M one fused multiply-add of the dot product,
+ *               qk_scale and -M (the product is not rounded before the subtraction), evaluated online
+ *               over the key blocks in ascending order, per half of each 32-key tile, the two halves
+ *               joined at the end
+ *   mass[i,j] = sum over the queries r of q-block i of (1/l_r) * sum over the keys c of key block j
+ *               of exp2(s[r,c] - M_r): per query the 16 keys of each half-tile in a fixed order, the
+ *               two halves, one product with 1/l_r, then the 32 queries by a butterfly. Every row of
+ *               mass sums to num_keep up to rounding.
+ *   po[i,j]   = storage(mass[i,j] / sum_j mass[i,j]): row-normalised in the storage dtype, the form
+ *               vb_block_mask_rule expects; the row sum runs per lane over j = lane, lane+64, ... and
+ *               then over the 64 lanes by a butterfly.
+ * Everything is taken relative to M_r, so scores of magnitude in the hundreds do not overflow.
+ * Deterministic: no floating-point atomics, every sum in an order fixed by the shape; two calls give
+ * the same bits. Three launches on `stream` (gather of the sampled rows, scores, row normalisation);
+ * nothing is allocated, nothing synchronises.
+ *
+ * q, k: [B,H,L,D] bf16/fp16, unit stride along D, the other strides (elements) in q_stride/k_stride:
+ * non-negative multiples of 8, bases 16-byte aligned; D = 64 or 128; nb <= 1024 (L <= 131072); every
+ * (b,h) slice of q and of k < 2 GiB. block must be 128. num_keep must be 32: 16 and 64 (which
+ * vb_mask_predict serves) are VB_ERR_UNSUPPORTED here, as are another D, nb > 1024 and a slice of
+ * 2 GiB or more. Null q, k, q_off, k_off or po, bad sizes, an unknown dtype, bad strides or alignment
+ * and a short or missing workspace are VB_ERR_INVALID. Every refusal happens before the first launch.
+ * workspace: device, 16-byte aligned, >= vb_mask_scores_mass_workspace_size(args) bytes (host
+ * arithmetic): the two gathered streams, B*H*2*nb*32*D elements, and B*H*nb*nb fp32 block masses.
+ * ========================================================================================== */
+typedef struct vb_mass_scores_args {
+  const void* q; const void* k;
+  int64_t q_stride[3]; int64_t k_stride[3];
+  const int32_t* rows;       /* device [L]: reordered position -> caller row, or NULL = identity */
+  const int32_t* q_off;      /* device [B,H,num_keep] int32 in [0, block): explicit offsets only */
+  const int32_t* k_off;
+  int B, H, L, D, block, num_keep;
+  float scale;               /* <= 0 -> D^-1/2 */
+  int dtype;
+  void* po;                  /* [B,H,nb,nb] storage dtype, contiguous */
+  float* mass;               /* [B,H,nb,nb] fp32 contiguous, or NULL (tests and calibration) */
+  void* workspace; uint64_t workspace_bytes;
+} vb_mass_scores_args;
+uint64_t vb_mask_scores_mass_workspace_size(const vb_mass_scores_args* args);
+int vb_mask_scores_mass(const vb_mass_scores_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,14 @@ heads), which gives the heads different concentrations. Per setting: the predict
 riding), the whole module call and its ratio to the default, the kept-block fraction, and the PSNR
 of the module output against dense SDPA on the same inputs.
 
+score=mass settings (ops.mask_scores_mass, the sampled softmax mass instead of the max proxy): `mass/energy`
+(the default rule on the new score; its fused-predictor column is its three launches plus the pooled K/V
+pass as a launch of its own, which is how the module runs it) and, at a budget EQUAL to the `energy`
+run's, `max/top-n@energy` and `mass/top-n@energy`: the n best blocks of every row of either score's po
+(n = the energy run's mean kept blocks per row, forced tail added), built with torch.topk and handed to
+the module as block_mask=. Their time columns include that torch code and are not a product path; their
+quality columns are what the score alone buys.
+
 --recall appends, per setting, the attention recall of its mask and the oracle recall of its budget
 (ops.mask_recall on the same q, k and mask: 30 probe queries per head, the module option's own
 positions; mean and smallest head), and one more setting, `energy/probe=recall`, whose call time
@@ -23,7 +31,7 @@ against `energy` is what the option costs, beside `judge`'s. The other columns a
 without the flag.
 
 usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--recall] [--out FILE.json]
-       rocprofv3 --kernel-trace --stats -d DIR -- python tools/rule_sweep.py --variant cog --one-call SETTING
+       rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- python tools/rule_sweep.py --variant cog --one-call SETTING
        (four module calls of one setting and nothing else: a kernel trace then shows its launches
        per call, tools/kstats.py DIR)"""
 import argparse
@@ -90,7 +98,35 @@ def settings(variant, H, recall=False):
     mods["judge/clamp(r,r)"] = mk(head_budget="judge", judge_clamp=(r, r))
     if recall:
         mods["energy/probe=recall"] = mk(probe="recall")
+    mods["mass/energy"] = mk(score="mass")
+    mods["mass/energy#aa"] = mk(score="mass")
+    for lab, score in EQUAL_BUDGET.items():
+        mods[lab] = mk(score=score)
     return mods
+
+
+EQUAL_BUDGET = {"max/top-n@energy": "max", "mass/top-n@energy": "mass"}
+
+
+def top_n_mask(m, q, k, n):
+    """The n best blocks per row of the module's score (its own draws and sampled tokens), plus the forced tail."""
+    B, H, L, _ = q.shape
+    rows = m._rows(q.device)
+    rq = torch.rand(B, H, 1, m.block, device=q.device)
+    rk = torch.rand(B, H, 1, m.block, device=q.device)
+    qo, ko = ops.sample_offsets(rq, rk, m.num_keep)
+    qo, ko = qo[:, :, 0], ko[:, :, 0]
+    if m.score == "mass":
+        po = ops.mask_scores_mass(q, k, qo, ko, rows=rows)
+    else:
+        po = ops.mask_predict(q, k, qo, ko, rows=rows, want_mask=False,
+                              long_rows=(L + 127) // 128 > ops.MAX_BLOCKS)[0]
+    mask = torch.zeros(po.shape, device=q.device, dtype=torch.uint8)
+    mask.scatter_(-1, torch.topk(po.float(), n, dim=-1).indices, 1)
+    if m.force_tail:
+        mask[..., -m.force_tail:] = 1
+        mask[..., -m.force_tail:, :] = 1
+    return mask
 
 
 def inputs(variant, H, D, dev, temps):
@@ -110,21 +146,36 @@ def sweep(variant, rounds, dev, temps=None, recall=False):
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     res = {}
 
-    def fns(m):
+    def fns(lab, m):
         copies = not (m._gather(D) and m._rows(dev) is not None)
         outs = ops.pool_kv_outputs(k, m.sample_gap, reordered=copies)
 
         def pred():
             torch.cuda.manual_seed(SEED)
+            if lab in EQUAL_BUDGET:
+                return top_n_mask(m, q, k, n_eq)
+            if m.score == "mass":   # the pooled pass is a launch of its own beside this score
+                r = m.predict_mask(q, k)
+                ops.pool_kv(k, v, m.sample_gap, m._rows(dev), reordered=copies)
+                return r
             return m.predict_mask(q, k, pool=(v, m.sample_gap, outs))
 
         def call():
             torch.cuda.manual_seed(SEED)
+            if lab in EQUAL_BUDGET:
+                return m(q, k, v, block_mask=top_n_mask(m, q, k, n_eq))
             return m(q, k, v)
         return {"pred_fused_ms": pred, "call_ms": call}
 
     with torch.no_grad():
-        work = {lab: fns(m) for lab, m in mods.items()}
+        torch.cuda.manual_seed(SEED)
+        mods["energy"](q, k, v)
+        # the energy run's mean kept blocks per row outside the forced tail rows, less the forced columns
+        # top_n_mask adds again; the kept column shows how close the budgets came out
+        ft = mods["energy"].force_tail
+        body = mods["energy"].last_mask[:, :, :mods["energy"].last_mask.shape[2] - ft]
+        n_eq = max(1, round(body.float().sum(-1).mean().item()) - ft)
+        work = {lab: fns(lab, m) for lab, m in mods.items()}
         for lab, m in mods.items():   # warm up; quality figures from this call
             out = work[lab]["call_ms"]()
             torch.cuda.synchronize()
@@ -151,7 +202,8 @@ def sweep(variant, rounds, dev, temps=None, recall=False):
     same = torch.equal(mods["judge/clamp(r,r)"].last_mask, mods["energy/uniform[H]"].last_mask)
     return {"variant": variant, "B": 1, "H": H, "L": L, "D": D, "nb": (L + 127) // 128,
             "inputs": "bench.local_qkv(seed 0)" + ("" if temps is None else f", q scaled per head {temps[0]}..{temps[1]}"),
-            "rounds": rounds, "calls_per_round": 5, "clamp_rr_mask_equals_uniform": same, "settings": res}
+            "rounds": rounds, "calls_per_round": 5, "clamp_rr_mask_equals_uniform": same,
+            "equal_budget_blocks_per_row": n_eq, "settings": res}
 
 
 def main():
@@ -180,7 +232,8 @@ def main():
         r = sweep(variant, a.rounds, dev, a.head_temps, a.recall)
         out["results"].append(r)
         print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks), inputs {r['inputs']}; "
-              f"judge/clamp(r,r) mask == energy/uniform[H] mask: {r['clamp_rr_mask_equals_uniform']}")
+              f"judge/clamp(r,r) mask == energy/uniform[H] mask: {r['clamp_rr_mask_equals_uniform']}; "
+              f"top-n@energy: n = {r['equal_budget_blocks_per_row']} blocks per row")
         print("  setting                      | fused pred ms (x energy) | call ms (x energy, x uniform[H]) | kept   | PSNR dB"
               + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else ""))
         for lab, d in r["settings"].items():

@@ -216,6 +216,21 @@ class RecallArgs(ctypes.Structure):
     ]
 
 
+class MassScoresArgs(ctypes.Structure):
+    """vb_mass_scores_args (include/vblade.h)."""
+    _fields_ = [
+        ("q", _vp), ("k", _vp),
+        ("q_stride", _i64x3), ("k_stride", _i64x3),
+        ("rows", _vp), ("q_off", _vp), ("k_off", _vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("L", ctypes.c_int), ("D", ctypes.c_int),
+        ("block", ctypes.c_int), ("num_keep", ctypes.c_int),
+        ("scale", ctypes.c_float),
+        ("dtype", ctypes.c_int),
+        ("po", _vp), ("mass", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 VB_JUDGE_MAX_SAMPLES = 64
 VB_RECALL_MAX_SAMPLES = 64
 VB_QK_BWD_MAX_GRID = 1024
@@ -287,6 +302,8 @@ SIGNATURES = {
         ctypes.c_int, _vp, _vp, _vp]),
     "vb_mask_recall_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(RecallArgs)]),
     "vb_mask_recall": (ctypes.c_int, [ctypes.POINTER(RecallArgs), _vp]),
+    "vb_mask_scores_mass_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(MassScoresArgs)]),
+    "vb_mask_scores_mass": (ctypes.c_int, [ctypes.POINTER(MassScoresArgs), _vp]),
 }
 
 _lib = None

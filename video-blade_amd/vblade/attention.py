@@ -160,6 +160,12 @@ class AdaptiveBlockSparseAttn(nn.Module):
     probe positions are drawn once, at construction, from a CPU generator seeded with ``probe_seed``
     (distinct reordered positions of the video part; the non-persistent buffer ``probe_pos``, which
     may be overwritten). Output, mask and random stream are those of a module without the option.
+    score: the block score the mask rule reads: "max" (default: the reference kernel's proxy, the largest
+    single-key probability ratio of a block, ops.mask_predict; the code path, launches and random stream
+    of a module without the option) or "mass" (the sampled softmax mass of the block, the sum-pooled
+    attention map the reference's docstring describes: ops.sample_offsets -> ops.mask_scores_mass ->
+    ops.block_mask_rule, the pooled K/V pass as its own launch). The same seed samples the same tokens
+    in both modes; every mask option above works with either. "mass" needs num_keep=32.
     """
 
     def __init__(self, variant: str = "cog", *, combine: str = "fused", **overrides):
@@ -171,7 +177,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                                "mask_head_mode", "order", "order_window", "persistent",
                                                "mask_mode", "init_k", "head_budget", "judge_samples",
                                                "judge_key_stride", "judge_top", "judge_clamp", "judge_seed",
-                                               "probe", "probe_samples", "probe_seed", "probe_every"}
+                                               "probe", "probe_samples", "probe_seed", "probe_every", "score"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
@@ -256,6 +262,12 @@ class AdaptiveBlockSparseAttn(nn.Module):
         if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
             raise ValueError(f"block must be 128 (the reference's only value) and num_keep one of "
                              f"{ops.NUM_KEEP_VALUES} (the reference's default is 32)")
+        self.score = cfg.get("score", "max")
+        if self.score not in ("max", "mass"):
+            raise ValueError(f"score must be 'max' or 'mass', got {self.score!r}")
+        if self.score == "mass" and self.num_keep != ops.MASS_NUM_KEEP:
+            raise ValueError(f"score='mass' samples {ops.MASS_NUM_KEEP} tokens per block only, got num_keep="
+                             f"{self.num_keep}")
         self.log_every = int(cfg["log_every"])
         self.mask_head_mode = cfg.get("mask_head_mode", "per_head")
         ops.mask_head_mode_code(self.mask_head_mode)   # validates
@@ -440,6 +452,11 @@ class AdaptiveBlockSparseAttn(nn.Module):
         budget = None
         if self.head_budget == "judge":
             budget = self._judge_budget(q, k, (L + self.block - 1) // self.block, judge_rows)
+        if self.score == "mass":
+            if pool is not None or staged_event is not None:
+                raise ValueError("score='mass': the pooled K/V pass is its own launch (ops.pool_kv); "
+                                 "pool= and staged_event= belong to the max predictor's launch")
+            return self._predict_mask_mass(q, k, q_off, k_off, count, rows_kept, budget)
         rand = philox = None
         if q_off is None and k_off is None:
             # the reference's two draws (:77-78, q first), generated and ranked inside the sampling
@@ -473,6 +490,31 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                     num_keep=self.num_keep)
         return po, mask
 
+    def _predict_mask_mass(self, q, k, q_off, k_off, count, rows_kept, budget):
+        """score="mass": the reference's two draws by torch.rand (q first: the values and the generator
+        state of the default path), then ops.sample_offsets -> ops.mask_scores_mass ->
+        ops.block_mask_rule with the call's rule."""
+        B, H, L, D = q.shape
+        nb = (L + self.block - 1) // self.block
+        if q_off is None and k_off is None:
+            q_off, k_off = draw_sample_offsets_qk(B, H, q.device, self.block, self.num_keep)
+        elif q_off is None:
+            q_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
+        elif k_off is None:
+            k_off = draw_sample_offsets(B, H, q.device, self.block, self.num_keep)
+        po = ops.mask_scores_mass(q, k, q_off, k_off, rows=self._rows(q.device))
+        rule = self._mask_rule(B, H, nb, q.device, budget)
+        thr, lo_r, hi_r = self.energy_threshold, self.min_retain_ratio, self.max_retain_ratio
+        if rule is not None:
+            # scalars of the options given as tensors are placeholders the rule's arrays replace
+            thr = 0.95 if isinstance(thr, torch.Tensor) else thr
+            lo_r = 1.0 if isinstance(lo_r, torch.Tensor) else lo_r
+            hi_r = 1.0 if isinstance(hi_r, torch.Tensor) else hi_r
+        lo, hi = retain_counts(nb, lo_r, hi_r, self.variant)
+        mask = ops.block_mask_rule(po, rule, energy_threshold=thr, min_keep=lo, max_keep=hi,
+                                   force_tail=self.force_tail, mask_count=count, rows_kept=rows_kept)
+        return po, mask
+
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *,
                 q_off: Optional[torch.Tensor] = None, k_off: Optional[torch.Tensor] = None,
                 block_mask: Optional[torch.Tensor] = None,
@@ -498,7 +540,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
             # contiguous copies the attention kernel streams by LDS-DMA; HBM-bound) runs inside the
             # predictor's score-kernel launch, beside the MFMA-bound score workgroups (overlap=True),
             # or after it (overlap=False)
-            ride = fused and self.overlap
+            ride = fused and self.overlap and self.score == "max"
             gather = self._gather(D)
             copies = not (gather and rows is not None)
             outs = ops.pool_kv_outputs(k, self.sample_gap, reordered=copies) if ride else None

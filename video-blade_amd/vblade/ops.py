@@ -872,6 +872,57 @@ def mask_recall(q, k, block_mask, probe_pos, *, rows=None, scale=None, want_rows
     return (recall, oracle, row_recall, row_oracle, row_kept) if want_rows else (recall, oracle)
 
 
+# ----------------------------------------------------------------------------------------------
+# mask predictor: the softmax-mass block score
+# ----------------------------------------------------------------------------------------------
+MASS_NUM_KEEP = 32   # the only sampling density vb_mask_scores_mass is built for
+
+
+def mask_scores_mass(q, k, q_off, k_off, *, rows=None, scale=None, want_mass: bool = False):
+    """vb_mask_scores_mass: the sampled softmax mass per (q-block, key-block) pair, row-normalised in
+    q.dtype: the score mask_predict's max proxy stands in for, in the form block_mask_rule takes.
+    q,k [B,H,L,D] (strided views are read in place); q_off/k_off int32 [B,H,32], the sampled offsets
+    of every 128-token block (sample_offsets' outputs); ``rows`` the reordered position -> caller row
+    index (None: identity). Returns po [B,H,nb,nb], or (po, mass) with ``want_mass``: the fp32 block
+    masses before the normalisation, each row summing to 32."""
+    if k.shape != q.shape or q.dim() != 4:
+        raise ValueError(f"mask_scores_mass: q and k must share a [B,H,L,D] shape, got {tuple(q.shape)} "
+                         f"and {tuple(k.shape)}")
+    dev = _require_gpu(q, k, q_off, k_off, rows)
+    B, H, L, D = q.shape
+    for name, off in (("q_off", q_off), ("k_off", k_off)):
+        if off.dim() != 3 or off.shape[0] != B or off.shape[1] != H:
+            raise ValueError(f"mask_scores_mass: {name} must be [B,H,{MASS_NUM_KEEP}] = [{B},{H},{MASS_NUM_KEEP}], "
+                             f"got {tuple(off.shape)}")
+        if off.shape[-1] != MASS_NUM_KEEP:
+            raise ValueError(f"mask_scores_mass: the mass score samples {MASS_NUM_KEEP} tokens per block only "
+                             f"(16 and 64 are mask_predict's), {name} is {off.shape[-1]} wide")
+    if rows is not None:
+        if rows.dtype != torch.int32 or rows.numel() != L:
+            raise ValueError(f"mask_scores_mass: rows must be int32 [{L}], got {rows.dtype} {tuple(rows.shape)}")
+        rows = rows.contiguous()
+    nb = (L + BLOCK - 1) // BLOCK
+    q_off = q_off.to(torch.int32).contiguous()
+    k_off = k_off.to(torch.int32).contiguous()
+    q, k = _aligned_bhld(q), _aligned_bhld(k)
+    a = _lib.MassScoresArgs()
+    a.B, a.H, a.L, a.D, a.block, a.num_keep = B, H, L, D, BLOCK, MASS_NUM_KEEP
+    a.scale = float(scale) if scale else 0.0
+    a.dtype = _dtype_code(q)
+    lib = _lib.load()
+    nbytes = int(lib.vb_mask_scores_mass_workspace_size(ctypes.byref(a)))
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    po = torch.empty(B, H, nb, nb, device=dev, dtype=q.dtype)
+    mass = torch.empty(B, H, nb, nb, device=dev, dtype=torch.float32) if want_mass else None
+    a.q, a.k = q.data_ptr(), k.data_ptr()
+    a.q_stride, a.k_stride = _s3(q), _s3(k)
+    a.rows, a.q_off, a.k_off = _ptr(rows), q_off.data_ptr(), k_off.data_ptr()
+    a.po, a.mass = po.data_ptr(), _ptr(mass)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    check(lib.vb_mask_scores_mass(ctypes.byref(a), _stream(dev)), "vb_mask_scores_mass")
+    return (po, mass) if want_mass else po
+
+
 def pool_kv_outputs(k, gap: int, reordered: bool = False):
     """Allocate pool_kv's outputs (kp, vp[, k_r, v_r]) on the current stream. A caller that launches
     pool_kv on a side stream allocates them BEFORE enqueueing other work whose temporaries could
