@@ -743,6 +743,75 @@ typedef struct vb_mass_scores_args {
 uint64_t vb_mask_scores_mass_workspace_size(const vb_mass_scores_args* args);
 int vb_mask_scores_mass(const vb_mass_scores_args* args, void* stream);
 
+/* ==========================================================================================
+ * Output-fidelity probe: the error of an attention output against exact dense attention, measured
+ * on a call's own q, k, v and out for S probe queries per head. Additive to ABI 4.
+ *
+ * The recall probe (vb_mask_recall) looks at the scores alone: it ignores V and the pooled branch
+ * and has no meaning for a graded (multi-level) mask. vb_attn_fidelity needs neither a mask nor an
+ * order (a softmax over all keys does not depend on the keys' order): it recomputes the dense output
+ * rows of the probe queries and compares `out` with them, whichever module or option produced `out`.
+ *
+ * All arithmetic fp32 unless stated. For every (b,h) and probe r < S:
+ *   g = clamp(probe_rows[r], 0, L-1), a CALLER row of q and out
+ *   t_j = <q_g, k_j> * qk_scale, j = 0 .. L-1 in caller order: MFMA with fp32 accumulation, the
+ *   product with qk_scale rounded once; qk_scale = fp32(scale) * fp32(1.44269504) as
+ *   vb_mask_scores_mass forms it, scale <= 0 -> D^-1/2. Only the L real rows take part: no padding.
+ *   The keys are cut into chunks of VB_FIDELITY_CHUNK = 512 consecutive keys, nc = ceil(L/512) of
+ *   them (the last holds L - 512*(nc-1)): a rule of L alone, never of the device, B or H.
+ *   Per chunk c: m_c = max t_j; e_j = exp2(t_j - m_c); l_c = sum e_j (per MFMA column over the
+ *   chunk's 32-key tiles in ascending order, then a butterfly over the 32 columns);
+ *   acc_c[d] = sum_j e_j * v_j[d], one fmaf per key in ascending key order, e_j never rounded below
+ *   fp32. (m_c, l_c, acc_c) are staged in the workspace.
+ *   Join, chunks in ascending order: m = max_c m_c; w_c = exp2(m_c - m); l = fmaf(l_c, w_c, l);
+ *   a[d] = fmaf(acc_c[d], w_c, a[d]); ref[d] = a[d] / l. Everything is relative to a maximum, so
+ *   scores of magnitude in the hundreds do not overflow.
+ *   row_err = sum_d (float(out[g,d]) - ref[d])^2 and row_sig = sum_d ref[d]^2: one fmaf per d, in
+ *   ascending d.  row_lse = ln(l) + m * ln 2 (the natural-log LSE of scale * <q,k>).
+ *   err[b,h], sig[b,h] = the sums of row_err, row_sig over r, added serially in r order;
+ *   peak[b,h] = max over r and d of |ref[d]|.
+ * SNR = 10 log10(sig / err) per head is the figure to log; peak^2 * S * D / err gives a sampled PSNR.
+ *
+ * q, k, v, out: [B,H,L,D] bf16/fp16, unit stride along D, the other strides (elements) in
+ * q_stride/k_stride/v_stride/out_stride: non-negative multiples of 8, bases 16-byte aligned; D = 64
+ * or 128; L <= 131072; every (b,h) slice < 2 GiB. probe_rows: DEVICE int32 [S], shared by all (b,h),
+ * S in [1, 64]; clamped to [0, L-1] by the kernel before any use. The kernels read no byte outside
+ * the L rows of each (b,h) slice.
+ * Outputs: err, sig fp32 [B,H] (required); peak fp32 [B,H], row_err, row_sig, row_lse fp32 [B,H,S]
+ * and ref fp32 [B,H,S,D] contiguous (each nullable).
+ * A null q, k, v, out, probe_rows, err or sig, bad sizes, S outside [1, 64], an unknown dtype, bases
+ * not 16-byte aligned or strides that are not non-negative multiples of 8 and a short or missing
+ * workspace are VB_ERR_INVALID before any launch; D not 64 or 128, L > 131072 and a (b,h) slice of
+ * 2 GiB or more are VB_ERR_UNSUPPORTED.
+ * workspace: device, 16-byte aligned, >= vb_attn_fidelity_workspace_size(args) bytes (host
+ * arithmetic): 4 * (B*H*S*nc*(D+2) + 3*B*H*S) rounded up to 16: the chunks' (m, l), their acc rows,
+ * and three results per row for the last launch.
+ * Deterministic: no floating-point atomics, every sum in an order fixed by the shape; two calls give
+ * the same bits, and a sample's results are the same bits alone or inside a larger batch. Three
+ * launches on `stream` (chunk partials, join, per-head sums); nothing is allocated, nothing
+ * synchronises.
+ * ========================================================================================== */
+#define VB_FIDELITY_MAX_SAMPLES 64
+#define VB_FIDELITY_CHUNK 512
+typedef struct vb_fidelity_args {
+  const void* q; const void* k; const void* v; const void* out;
+  int64_t q_stride[3]; int64_t k_stride[3]; int64_t v_stride[3]; int64_t out_stride[3];
+  const int32_t* probe_rows; /* device [S]: caller rows of the probe queries */
+  int B, H, L, D, S;
+  float scale;               /* <= 0 -> D^-1/2 */
+  int dtype;
+  float* err;                /* [B,H] */
+  float* sig;                /* [B,H] */
+  float* peak;               /* [B,H] or NULL */
+  float* row_err;            /* [B,H,S] or NULL */
+  float* row_sig;            /* [B,H,S] or NULL */
+  float* row_lse;            /* [B,H,S] or NULL */
+  float* ref;                /* [B,H,S,D] or NULL */
+  void* workspace; uint64_t workspace_bytes;
+} vb_fidelity_args;
+uint64_t vb_attn_fidelity_workspace_size(const vb_fidelity_args* args);
+int vb_attn_fidelity(const vb_fidelity_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

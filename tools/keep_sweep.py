@@ -15,7 +15,13 @@ module output against dense SDPA on the same inputs.
 positions; mean and smallest head), and one more module, keep 32 with probe="recall", whose call time
 against keep 32 is what the option costs. The other columns are computed as without the flag.
 
-usage: python tools/keep_sweep.py [--variant cog|wan|both] [--rounds 15] [--recall] [--out FILE.json]"""
+--fidelity appends, per density, what ops.attn_fidelity measures on its own output (30 probe queries per
+head, the module option's own rows): the SNR against exact dense rows over all heads (and the smallest
+head's) and a sampled PSNR, 10 log10(peak^2 S D H / sum err), to be read against the full-tensor PSNR
+column; and two more modules: keep 32 with probe="fidelity", whose call time against keep 32 is what the
+option costs, and the multi-level (VBench) module at keep 32 (no predictor-only columns).
+
+usage: python tools/keep_sweep.py [--variant cog|wan|both] [--rounds 15] [--recall] [--fidelity] [--out FILE.json]"""
 import argparse
 import json
 import math
@@ -29,7 +35,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "video-blade_amd"))
 sys.path.insert(0, ROOT)
 import vblade  # noqa: E402
-from vblade import ops  # noqa: E402
+from vblade import multilevel, ops  # noqa: E402
+from vblade.attention import VARIANT_DEFAULTS  # noqa: E402
 from bench import local_qkv  # noqa: E402
 
 KEEPS = (16, 32, 64)
@@ -62,7 +69,21 @@ def recall_of(m, q, k, pos):
             "oracle_recall_mean": ora.mean().item(), "oracle_recall_min_head": ora.min().item()}
 
 
-def sweep(variant, rounds, dev, recall=False):
+def fidelity_of(q, k, v, out, prows):
+    """SNR (all heads, smallest head) and the sampled PSNR of an output, from ops.attn_fidelity."""
+    err, sig, peak = (t.double() for t in ops.attn_fidelity(q, k, v, out, prows))
+    S, D = prows.numel(), q.shape[-1]
+    snr = ops.fidelity_snr_db(err, sig)
+    return {"fidelity_snr_db": 10 * math.log10(sig.sum().item() / max(err.sum().item(), 1e-300)),
+            "fidelity_snr_min_head_db": snr.min().item(),
+            "fidelity_sampled_psnr_db": 10 * math.log10(peak.max().item() ** 2 * S * D * err.numel()
+                                                        / max(err.sum().item(), 1e-300))}
+
+
+MULTILEVEL = "ml/32"
+
+
+def sweep(variant, rounds, dev, recall=False, fidelity=False):
     H, D = (48, 64) if variant == "cog" else (12, 128)
     q, k, v = local_qkv(variant, H, D, 0, dev)
     L = q.shape[2]
@@ -73,10 +94,21 @@ def sweep(variant, rounds, dev, recall=False):
     if recall:
         mods["32+probe"] = vblade.AdaptiveBlockSparseAttn(variant, log_every=0, num_keep=32, probe="recall")
         pos = mods["32+probe"].probe_pos.to(dev)
+    prows = None
+    if fidelity:
+        mods["32+fid"] = vblade.AdaptiveBlockSparseAttn(variant, log_every=0, num_keep=32, probe="fidelity")
+        prows = mods["32+fid"].probe_rows.to(dev)
+        grid = {n: VARIANT_DEFAULTS[variant][n] for n in ("width", "height", "depth", "text_length")}
+        mods[MULTILEVEL] = multilevel.AdaptiveBlockSparseAttnTrain(log_every=0, num_keep=32, **grid)
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     res, masks = {}, {}
 
     def fns(m):
+        if isinstance(m, multilevel.AdaptiveBlockSparseAttnTrain):
+            def ml_call():
+                torch.cuda.manual_seed(SEED)
+                return m(q, k, v)
+            return {"call_ms": ml_call}
         copies = not (m._gather(D) and m._rows(dev) is not None)
         outs = ops.pool_kv_outputs(k, m.sample_gap, reordered=copies)
 
@@ -100,25 +132,32 @@ def sweep(variant, rounds, dev, recall=False):
             torch.cuda.synchronize()
             mask = m.last_mask.clone()
             masks[lab] = mask
-            res[lab] = {"num_keep": m.num_keep, "kept_fraction": mask.float().mean().item(),
+            kept = multilevel.density(m.mask_ratios) if lab == MULTILEVEL else mask.float().mean().item()
+            res[lab] = {"num_keep": m.num_keep, "kept_fraction": kept,
                         "psnr_vs_dense_db": psnr(out, dense)}
-            if recall:
+            if recall and lab != MULTILEVEL:
                 res[lab].update(recall_of(m, q, k, pos))
+            if fidelity:
+                res[lab].update(fidelity_of(q, k, v, out, prows))
             for f in ("pred_fused_ms", "pred_scores_ms"):
-                work[lab][f]()
+                if f in work[lab]:
+                    work[lab][f]()
         times = {lab: {f: [] for f in work[lab]} for lab in mods}
         for _ in range(rounds):
             for f in ("pred_fused_ms", "pred_scores_ms", "call_ms"):
                 for lab in mods:
-                    times[lab][f].append(timed(work[lab][f]))
+                    if f in work[lab]:
+                        times[lab][f].append(timed(work[lab][f]))
     for lab in mods:
         for f, ts in times[lab].items():
             res[lab][f] = statistics.median(ts)
             res[lab][f + "_min"] = min(ts)
-        res[lab]["mask_equal_to_keep32"] = (masks[lab] == masks["32"]).float().mean().item()
+        if lab != MULTILEVEL:   # a level mask is graded 0/1/2/4/8: not comparable entry by entry
+            res[lab]["mask_equal_to_keep32"] = (masks[lab] == masks["32"]).float().mean().item()
     for lab in mods:
         for f in ("pred_fused_ms", "pred_scores_ms", "call_ms"):
-            res[lab][f.replace("_ms", "_vs_keep32")] = res[lab][f] / res["32"][f]
+            if f in res[lab]:
+                res[lab][f.replace("_ms", "_vs_keep32")] = res[lab][f] / res["32"][f]
     return {"variant": variant, "B": 1, "H": H, "L": L, "D": D, "nb": (L + 127) // 128,
             "inputs": "bench.local_qkv(seed 0)", "rounds": rounds, "calls_per_round": 5, "densities": res}
 
@@ -129,24 +168,32 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--out", default=None)
     ap.add_argument("--recall", action="store_true")
+    ap.add_argument("--fidelity", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda")
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
-        r = sweep(variant, a.rounds, dev, a.recall)
+        r = sweep(variant, a.rounds, dev, a.recall, a.fidelity)
         out["results"].append(r)
         print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks)")
         print("  keep | fused pred ms (x32) | scores-only ms (x32) | call ms (x32) | kept | == keep32 | PSNR dB"
-              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else ""))
+              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else "")
+              + (" | fidelity SNR dB (min head) | sampled PSNR dB" if a.fidelity else ""))
         for lab, d in r["densities"].items():
             extra = ""
             if a.recall:
                 extra = (f" | {d['recall_mean']:.4f} ({d['recall_min_head']:.4f}) | "
-                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})")
-            print(f"  {lab:>5} | {d['pred_fused_ms']:.4f} ({d['pred_fused_vs_keep32']:.3f}) | "
-                  f"{d['pred_scores_ms']:.4f} ({d['pred_scores_vs_keep32']:.3f}) | "
+                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})"
+                         if "recall_mean" in d else " | - | -")
+            if a.fidelity:
+                extra += (f" | {d['fidelity_snr_db']:.2f} ({d['fidelity_snr_min_head_db']:.2f}) | "
+                          f"{d['fidelity_sampled_psnr_db']:.2f}")
+            pred = (f"{d['pred_fused_ms']:.4f} ({d['pred_fused_vs_keep32']:.3f}) | "
+                    f"{d['pred_scores_ms']:.4f} ({d['pred_scores_vs_keep32']:.3f})" if "pred_fused_ms" in d else "- | -")
+            same = f"{d['mask_equal_to_keep32']:.4f}" if "mask_equal_to_keep32" in d else "-"
+            print(f"  {lab:>6} | {pred} | "
                   f"{d['call_ms']:.4f} ({d['call_vs_keep32']:.3f}) | {d['kept_fraction']:.4f} | "
-                  f"{d['mask_equal_to_keep32']:.4f} | {d['psnr_vs_dense_db']:.2f}{extra}", flush=True)
+                  f"{same} | {d['psnr_vs_dense_db']:.2f}{extra}", flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

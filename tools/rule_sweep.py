@@ -30,7 +30,15 @@ positions; mean and smallest head), and one more setting, `energy/probe=recall`,
 against `energy` is what the option costs, beside `judge`'s. The other columns are computed as
 without the flag.
 
-usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--recall] [--out FILE.json]
+--fidelity appends, per setting, what ops.attn_fidelity measures on the setting's own output (30 probe
+queries per head, the module option's own rows): the SNR against exact dense rows over all heads (and the
+smallest head's) and a sampled PSNR, 10 log10(peak^2 S D H / sum err) with the probe's own peak, to be read
+against the full-tensor "PSNR dB" column; and two more settings: `energy/probe=fidelity`, whose call time
+against `energy` is what the option costs (beside `energy/probe=recall` with --recall), and `multilevel`,
+the multi-level (VBench) module on the same inputs (its predictor column is predict_level_mask with the
+pyramid pass riding, its kept column the reported density).
+
+usage: python tools/rule_sweep.py [--variant cog|wan|both] [--rounds 15] [--head-temps LO HI] [--recall] [--fidelity] [--out FILE.json]
        rocprofv3 --kernel-trace --stats -d DIR -o run --output-format csv -- python tools/rule_sweep.py --variant cog --one-call SETTING
        (four module calls of one setting and nothing else: a kernel trace then shows its launches
        per call, tools/kstats.py DIR)"""
@@ -47,7 +55,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "video-blade_amd"))
 sys.path.insert(0, ROOT)
 import vblade  # noqa: E402
-from vblade import ops  # noqa: E402
+from vblade import multilevel, ops  # noqa: E402
 from vblade.attention import VARIANT_DEFAULTS  # noqa: E402
 from bench import local_qkv  # noqa: E402
 
@@ -81,7 +89,18 @@ def recall_of(m, q, k, pos):
             "oracle_recall_mean": ora.mean().item(), "oracle_recall_min_head": ora.min().item()}
 
 
-def settings(variant, H, recall=False):
+def fidelity_of(q, k, v, out, prows):
+    """SNR (all heads, smallest head) and the sampled PSNR of an output, from ops.attn_fidelity."""
+    err, sig, peak = (t.double() for t in ops.attn_fidelity(q, k, v, out, prows))
+    S, D = prows.numel(), q.shape[-1]
+    snr = ops.fidelity_snr_db(err, sig)
+    return {"fidelity_snr_db": 10 * math.log10(sig.sum().item() / max(err.sum().item(), 1e-300)),
+            "fidelity_snr_min_head_db": snr.min().item(),
+            "fidelity_sampled_psnr_db": 10 * math.log10(peak.max().item() ** 2 * S * D * err.numel()
+                                                        / max(err.sum().item(), 1e-300))}
+
+
+def settings(variant, H, recall=False, fidelity=False):
     d = VARIANT_DEFAULTS[variant]
     mk = lambda **kw: vblade.AdaptiveBlockSparseAttn(variant, log_every=0, **kw)  # noqa: E731
     mods = {"energy": mk(), "energy#aa": mk()}
@@ -98,6 +117,10 @@ def settings(variant, H, recall=False):
     mods["judge/clamp(r,r)"] = mk(head_budget="judge", judge_clamp=(r, r))
     if recall:
         mods["energy/probe=recall"] = mk(probe="recall")
+    if fidelity:
+        mods["energy/probe=fidelity"] = mk(probe="fidelity")
+        grid = {n: d[n] for n in ("width", "height", "depth", "text_length")}
+        mods[MULTILEVEL] = multilevel.AdaptiveBlockSparseAttnTrain(log_every=0, **grid)
     mods["mass/energy"] = mk(score="mass")
     mods["mass/energy#aa"] = mk(score="mass")
     for lab, score in EQUAL_BUDGET.items():
@@ -105,6 +128,7 @@ def settings(variant, H, recall=False):
     return mods
 
 
+MULTILEVEL = "multilevel"
 EQUAL_BUDGET = {"max/top-n@energy": "max", "mass/top-n@energy": "mass"}
 
 
@@ -137,16 +161,31 @@ def inputs(variant, H, D, dev, temps):
     return q, k, v
 
 
-def sweep(variant, rounds, dev, temps=None, recall=False):
+def sweep(variant, rounds, dev, temps=None, recall=False, fidelity=False):
     H, D = (48, 64) if variant == "cog" else (12, 128)
     q, k, v = inputs(variant, H, D, dev, temps)
     L = q.shape[2]
-    mods = settings(variant, H, recall)
+    mods = settings(variant, H, recall, fidelity)
     pos = mods["energy/probe=recall"].probe_pos.to(dev) if recall else None
+    prows = mods["energy/probe=fidelity"].probe_rows.to(dev) if fidelity else None
     dense = torch.nn.functional.scaled_dot_product_attention(q, k, v)
     res = {}
 
+    def ml_fns(m):
+        outs = ops.kv_pyramid_outputs(k)
+
+        def pred():
+            torch.cuda.manual_seed(SEED)
+            return multilevel.predict_level_mask(q, k, rows=m._rows(dev), mask_ratios=m.mask_ratios, pyr=(v, outs))
+
+        def call():
+            torch.cuda.manual_seed(SEED)
+            return m(q, k, v)
+        return {"pred_fused_ms": pred, "call_ms": call}
+
     def fns(lab, m):
+        if lab == MULTILEVEL:
+            return ml_fns(m)
         copies = not (m._gather(D) and m._rows(dev) is not None)
         outs = ops.pool_kv_outputs(k, m.sample_gap, reordered=copies)
 
@@ -179,10 +218,13 @@ def sweep(variant, rounds, dev, temps=None, recall=False):
         for lab, m in mods.items():   # warm up; quality figures from this call
             out = work[lab]["call_ms"]()
             torch.cuda.synchronize()
-            res[lab] = {"kept_fraction": m.last_mask.float().mean().item(), "psnr_vs_dense_db": psnr(out, dense)}
-            if recall:
+            kept = multilevel.density(m.mask_ratios) if lab == MULTILEVEL else m.last_mask.float().mean().item()
+            res[lab] = {"kept_fraction": kept, "psnr_vs_dense_db": psnr(out, dense)}
+            if recall and lab != MULTILEVEL:
                 res[lab].update(recall_of(m, q, k, pos))
-            if m.head_budget == "judge":
+            if fidelity:
+                res[lab].update(fidelity_of(q, k, v, out, prows))
+            if lab != MULTILEVEL and m.head_budget == "judge":
                 b = m.last_head_budget.flatten().tolist()
                 sp = m.last_head_sparsity.flatten().tolist()
                 res[lab].update(head_budget_min=min(b), head_budget_max=max(b), head_budget_mean=sum(b) / len(b),
@@ -214,33 +256,41 @@ def main():
     ap.add_argument("--one-call", default=None, metavar="SETTING")
     ap.add_argument("--head-temps", type=float, nargs=2, default=None, metavar=("LO", "HI"))
     ap.add_argument("--recall", action="store_true")
+    ap.add_argument("--fidelity", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda")
     if a.one_call:
         variant = "cog" if a.variant == "both" else a.variant
         H, D = (48, 64) if variant == "cog" else (12, 128)
-        m = settings(variant, H, a.recall)[a.one_call]
+        m = settings(variant, H, a.recall, a.fidelity)[a.one_call]
         q, k, v = inputs(variant, H, D, dev, a.head_temps)
         with torch.no_grad():
             for _ in range(4):
                 m(q, k, v)
         torch.cuda.synchronize()
-        print(f"{variant} {a.one_call}: 4 calls, kept {m.last_mask.float().mean().item():.4f}")
+        print(f"{variant} {a.one_call}: 4 calls, kept {m.last_mask.float().mean().item():.4f}"
+              + (f", fidelity SNR dB per head {[round(x, 2) for x in m.fidelity.flatten().tolist()]}"
+                 if getattr(m, "fidelity", None) is not None else ""))
         return
     out = {"device": torch.cuda.get_device_name(0), "results": []}
     for variant in (["cog", "wan"] if a.variant == "both" else [a.variant]):
-        r = sweep(variant, a.rounds, dev, a.head_temps, a.recall)
+        r = sweep(variant, a.rounds, dev, a.head_temps, a.recall, a.fidelity)
         out["results"].append(r)
         print(f"{variant}: H={r['H']} L={r['L']} D={r['D']} ({r['nb']} blocks), inputs {r['inputs']}; "
               f"judge/clamp(r,r) mask == energy/uniform[H] mask: {r['clamp_rr_mask_equals_uniform']}; "
               f"top-n@energy: n = {r['equal_budget_blocks_per_row']} blocks per row")
         print("  setting                      | fused pred ms (x energy) | call ms (x energy, x uniform[H]) | kept   | PSNR dB"
-              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else ""))
+              + (" | recall mean (min head) | oracle recall mean (min head)" if a.recall else "")
+              + (" | fidelity SNR dB (min head) | sampled PSNR dB" if a.fidelity else ""))
         for lab, d in r["settings"].items():
             extra = ""
             if a.recall:
                 extra = (f" | {d['recall_mean']:.4f} ({d['recall_min_head']:.4f}) | "
-                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})")
+                         f"{d['oracle_recall_mean']:.4f} ({d['oracle_recall_min_head']:.4f})"
+                         if "recall_mean" in d else " | - | -")
+            if a.fidelity:
+                extra += (f" | {d['fidelity_snr_db']:.2f} ({d['fidelity_snr_min_head_db']:.2f}) | "
+                          f"{d['fidelity_sampled_psnr_db']:.2f}")
             if "head_budget_min" in d:
                 extra += (f" | budgets {d['head_budget_min']}..{d['head_budget_max']} (mean {d['head_budget_mean']:.2f}), "
                          f"sparsity {d['head_sparsity_min']:.3f}..{d['head_sparsity_max']:.3f}")

@@ -231,8 +231,26 @@ class MassScoresArgs(ctypes.Structure):
     ]
 
 
+class FidelityArgs(ctypes.Structure):
+    """vb_fidelity_args (include/vblade.h)."""
+    _fields_ = [
+        ("q", _vp), ("k", _vp), ("v", _vp), ("out", _vp),
+        ("q_stride", _i64x3), ("k_stride", _i64x3), ("v_stride", _i64x3), ("out_stride", _i64x3),
+        ("probe_rows", _vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("L", ctypes.c_int), ("D", ctypes.c_int),
+        ("S", ctypes.c_int),
+        ("scale", ctypes.c_float),
+        ("dtype", ctypes.c_int),
+        ("err", _vp), ("sig", _vp), ("peak", _vp),
+        ("row_err", _vp), ("row_sig", _vp), ("row_lse", _vp), ("ref", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_uint64),
+    ]
+
+
 VB_JUDGE_MAX_SAMPLES = 64
 VB_RECALL_MAX_SAMPLES = 64
+VB_FIDELITY_MAX_SAMPLES = 64
+VB_FIDELITY_CHUNK = 512
 VB_QK_BWD_MAX_GRID = 1024
 VB_QK_NORM_NONE, VB_QK_NORM_LAYER_HEAD, VB_QK_NORM_RMS_ROW = 0, 1, 2
 VB_QK_ROPE_NONE, VB_QK_ROPE_REAL, VB_QK_ROPE_COMPLEX = 0, 1, 2
@@ -304,6 +322,8 @@ SIGNATURES = {
     "vb_mask_recall": (ctypes.c_int, [ctypes.POINTER(RecallArgs), _vp]),
     "vb_mask_scores_mass_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(MassScoresArgs)]),
     "vb_mask_scores_mass": (ctypes.c_int, [ctypes.POINTER(MassScoresArgs), _vp]),
+    "vb_attn_fidelity_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(FidelityArgs)]),
+    "vb_attn_fidelity": (ctypes.c_int, [ctypes.POINTER(FidelityArgs), _vp]),
 }
 
 _lib = None

@@ -117,6 +117,47 @@ class GilbertRearranger(nn.Module):
         return res
 
 
+def parse_probe(probe, allowed):
+    """The ``probe`` option as a tuple of names: None, one of ``allowed``, or a tuple or list of distinct
+    ones. Anything else raises ValueError."""
+    if probe is None:
+        return ()
+    names = (probe,) if isinstance(probe, str) else probe
+    if (not isinstance(names, (tuple, list)) or not names or len(set(names)) != len(names)
+            or any(not isinstance(n, str) or n not in allowed for n in names)):
+        forms = " or ".join(repr(n) for n in allowed)
+        raise ValueError(f"probe must be None, {forms}" + (", or a tuple of both" if len(allowed) > 1 else "")
+                         + f", got {probe!r}")
+    return tuple(names)
+
+
+def probe_fidelity(module, q, k, v, out):
+    """One fidelity measurement of a module call (the adaptive and the multi-level module share it):
+    ops.attn_fidelity under no_grad on the detached tensors, ``last_fidelity_*`` and the running sums
+    on the device."""
+    rows = module.probe_rows
+    if rows.device != q.device or rows.dtype != torch.int32:
+        rows = rows.to(device=q.device, dtype=torch.int32)
+        module.probe_rows = rows
+    with torch.no_grad():
+        err, sig, peak = ops.attn_fidelity(q.detach(), k.detach(), v.detach(), out.detach(), rows)
+        sums = module._fidelity_sums
+        if sums is None or sums.shape[1:] != err.shape or sums.device != err.device:
+            sums = module._fidelity_sums = torch.zeros(2, *err.shape, device=err.device, dtype=torch.float32)
+            module._fidelity_count = 0
+        sums[0].add_(err)
+        sums[1].add_(sig)
+    module._fidelity_count += 1
+    module.last_fidelity_err, module.last_fidelity_sig, module.last_fidelity_peak = err, sig, peak
+
+
+def fidelity_snr(module):
+    if module._fidelity_sums is None or module._fidelity_count == 0:
+        return None
+    sums = module._fidelity_sums.cpu()
+    return ops.fidelity_snr_db(sums[0], sums[1]).float()
+
+
 class AdaptiveBlockSparseAttn(nn.Module):
     """``inner_attention(q, k, v) -> out`` with q,k,v,out [B,H,L,D] bf16/fp16 on a HIP device.
 
@@ -160,6 +201,15 @@ class AdaptiveBlockSparseAttn(nn.Module):
     probe positions are drawn once, at construction, from a CPU generator seeded with ``probe_seed``
     (distinct reordered positions of the video part; the non-persistent buffer ``probe_pos``, which
     may be overwritten). Output, mask and random stream are those of a module without the option.
+    probe "fidelity" (alone, or with "recall" as a tuple or list of both): every ``probe_every``-th call
+    measures, after its output exists, the error of that output against exact dense attention on its own
+    q, k and v for the same ``probe_samples`` queries (ops.attn_fidelity: V, the pooled branch and the
+    combine included, which recall leaves out). The positions are the recall probe's draw, mapped once
+    through the rearranger's ``rows`` into caller rows (the non-persistent buffer ``probe_rows``, which
+    may be overwritten; without the reorder a position is its own caller row). ``last_fidelity_err``,
+    ``last_fidelity_sig`` and ``last_fidelity_peak`` (fp32 [B,H]) stay on the device; ``fidelity`` reads
+    the per-head SNR in dB over the probed calls. Inference and autograd calls are probed alike, under
+    no_grad on detached tensors.
     score: the block score the mask rule reads: "max" (default: the reference kernel's proxy, the largest
     single-key probability ratio of a block, ops.mask_predict; the code path, launches and random stream
     of a module without the option) or "mass" (the sampled softmax mass of the block, the sum-pooled
@@ -240,9 +290,13 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self._probe_calls = 0      # host counter of forward calls, probed or not
         self._recall_sums = None   # fp32 [2,B,H] on the device: recall and oracle recall, summed over the probed calls
         self._recall_count = 0
-        if self.probe not in (None, "recall"):
-            raise ValueError(f"probe must be None or 'recall', got {self.probe!r}")
-        if self.probe == "recall":
+        self.last_fidelity_err: Optional[torch.Tensor] = None
+        self.last_fidelity_sig: Optional[torch.Tensor] = None
+        self.last_fidelity_peak: Optional[torch.Tensor] = None
+        self._fidelity_sums = None   # fp32 [2,B,H] on the device: err and sig, summed over the probed calls
+        self._fidelity_count = 0
+        self._probes = parse_probe(self.probe, ("recall", "fidelity"))
+        if self._probes:
             if not 1 <= self.probe_samples <= ops.RECALL_MAX_SAMPLES:
                 raise ValueError(f"probe_samples must be in [1, {ops.RECALL_MAX_SAMPLES}], got {self.probe_samples}")
             if self.probe_every < 1:
@@ -256,7 +310,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
             gen = torch.Generator(device="cpu")
             gen.manual_seed(self.probe_seed)
             pos = torch.randperm(video, generator=gen)[:self.probe_samples]
-            self.register_buffer("probe_pos", pos.to(torch.int32), persistent=False)
+            if "recall" in self._probes:
+                self.register_buffer("probe_pos", pos.to(torch.int32), persistent=False)
         self.block = int(cfg.get("block", 128))
         self.num_keep = int(cfg.get("num_keep", 32))
         if self.block != 128 or self.num_keep not in ops.NUM_KEEP_VALUES:
@@ -273,6 +328,10 @@ class AdaptiveBlockSparseAttn(nn.Module):
         ops.mask_head_mode_code(self.mask_head_mode)   # validates
         self.gilbert_rearranger = GilbertRearranger(cfg["width"], cfg["height"], cfg["depth"],
                                                     self.text_length)
+        if "fidelity" in self._probes:
+            # the same queries as caller rows: the fidelity probe takes no order
+            prow = self.gilbert_rearranger.rows[pos.long()] if self.use_rearrange else pos
+            self.register_buffer("probe_rows", prow.to(torch.int32).clone(), persistent=False)
         # running sparsity statistic kept on the device (the reference's .item() per call, :415,
         # is replaced by a device counter; read it through .sparsity)
         self.sparsity_counter = 0
@@ -422,6 +481,18 @@ class AdaptiveBlockSparseAttn(nn.Module):
         mean = (self._recall_sums / self._recall_count).cpu()
         return mean[0], mean[1]
 
+    def _probe_fidelity(self, q, k, v, out):
+        """probe="fidelity": ops.attn_fidelity on this call's q, k, v and the output it returns. Three
+        launches on the current stream; the results stay on the device."""
+        probe_fidelity(self, q, k, v, out)
+
+    @property
+    def fidelity(self):
+        """Per-head SNR in dB of the output against dense attention, fp32 [B,H], from the sums of sig and
+        err over the probed calls, or None before the first. Reading it synchronises once; the forward
+        never does."""
+        return fidelity_snr(self)
+
     def _mask_rule(self, B, H, nb, device, max_keep=None):
         """The ops.MaskRule of a call, or None when the options are the scalar energy rule's.
         ``max_keep``: the judge's int32 [B,H] counts, in place of max_retain_ratio's."""
@@ -567,8 +638,10 @@ class AdaptiveBlockSparseAttn(nn.Module):
             # head_mask_type's ones read literally: every head uses base_blockmask head 0 (a
             # head-stride-0 view; the kernels index the mask through its strides)
             mask = mask[:, :1].expand(B, H, mask.shape[2], mask.shape[3])
-        if self.probe == "recall":
-            if self._probe_calls % self.probe_every == 0:
+        probing = False
+        if self._probes:
+            probing = self._probe_calls % self.probe_every == 0
+            if probing and "recall" in self._probes:
                 self._probe_recall(q, k, mask, rows)
             self._probe_calls += 1
         if not fused:
@@ -599,6 +672,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
                 ev.append((e0, e1))
+        if probing and "fidelity" in self._probes:
+            self._probe_fidelity(q, k, v, out)
         if self.log_every and self.sparsity_counter % self.log_every == 0:
             print(f"sparsity: {self.sparsity}")
         return out

@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .attention import GilbertRearranger, draw_sample_offsets_qk
+from .attention import GilbertRearranger, draw_sample_offsets_qk, fidelity_snr, parse_probe, probe_fidelity
 
 # Triton/cogvideo_newattn.py:12-24
 MASK_RATIOS = dict(ops.ML_MASK_RATIOS)
@@ -136,11 +136,18 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
     include/vblade.h, vb_ml_attn_fwd)."""
 
     def __init__(self, *, mask_ratios=None, ref_tail: bool = True, log_every: int = 600,
-                 overlap: bool = True, persistent: bool = False, num_keep: int = 32, **overrides):
+                 overlap: bool = True, persistent: bool = False, num_keep: int = 32,
+                 probe=None, probe_samples: int = 30, probe_seed: int = 0, probe_every: int = 1, **overrides):
         """num_keep: tokens the mask predictor samples per block (16, 32 or 64; default 32).
         overlap: run the KV pyramid pass inside the predictor's launch (True) or as its own
         launch after it. persistent: the attention launch is resident-sized and pulls q-blocks
-        from per-XCD work queues (scheduling only; see attention.PERSISTENT_DEFAULT)."""
+        from per-XCD work queues (scheduling only; see attention.PERSISTENT_DEFAULT).
+        probe: None (default) or "fidelity": every ``probe_every``-th call measures the error of its
+        output against exact dense attention for ``probe_samples`` queries of the video part
+        (ops.attn_fidelity), as AdaptiveBlockSparseAttn's option of that name does: the same draw from
+        ``probe_seed``, the buffer ``probe_rows``, ``last_fidelity_err`` / ``_sig`` / ``_peak`` on the
+        device and the ``fidelity`` property. Output, mask and random stream are those of a module
+        without the option."""
         super().__init__()
         cfg = dict(DEFAULTS)
         unknown = set(overrides) - set(cfg)
@@ -165,6 +172,44 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
         self.num_keep = int(num_keep)
         if self.num_keep not in ops.NUM_KEEP_VALUES:
             raise ValueError(f"num_keep must be one of {ops.NUM_KEEP_VALUES}")
+        self.probe = probe
+        self.probe_samples = int(probe_samples)
+        self.probe_seed = int(probe_seed)
+        self.probe_every = int(probe_every)
+        self.last_fidelity_err: Optional[torch.Tensor] = None
+        self.last_fidelity_sig: Optional[torch.Tensor] = None
+        self.last_fidelity_peak: Optional[torch.Tensor] = None
+        self._probe_calls = 0
+        self._fidelity_sums = None
+        self._fidelity_count = 0
+        self._probes = parse_probe(probe, ("fidelity",))
+        if self._probes:
+            if not 1 <= self.probe_samples <= ops.FIDELITY_MAX_SAMPLES:
+                raise ValueError(f"probe_samples must be in [1, {ops.FIDELITY_MAX_SAMPLES}], got {self.probe_samples}")
+            if self.probe_every < 1:
+                raise ValueError(f"probe_every must be >= 1, got {self.probe_every}")
+            video = int(cfg["width"]) * int(cfg["height"]) * int(cfg["depth"])
+            if self.probe_samples > video:
+                raise ValueError(f"probe_samples {self.probe_samples} exceeds the {video} video tokens")
+            # AdaptiveBlockSparseAttn's draw: distinct reordered positions of the video part, once, from
+            # a CPU generator, mapped into caller rows
+            gen = torch.Generator(device="cpu")
+            gen.manual_seed(self.probe_seed)
+            pos = torch.randperm(video, generator=gen)[:self.probe_samples]
+            prow = self.gilbert_rearranger.rows[pos.long()] if self.use_rearrange else pos
+            self.register_buffer("probe_rows", prow.to(torch.int32).clone(), persistent=False)
+
+    @property
+    def fidelity(self):
+        """Per-head SNR in dB of the output against dense attention, fp32 [B,H], over the probed calls,
+        or None before the first. Reading it synchronises once; the forward never does."""
+        return fidelity_snr(self)
+
+    def _probe(self, q, k, v, out):
+        if self._probes:
+            if self._probe_calls % self.probe_every == 0:
+                probe_fidelity(self, q, k, v, out)
+            self._probe_calls += 1
 
     def _rows(self, device):
         if not self.use_rearrange:
@@ -191,6 +236,7 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
                 else:
                     mask = level_mask.to(torch.uint8).contiguous()
             out = _SparseAttention.apply(q, k, v, mask, q.shape[-1] ** -0.5, self.ref_tail, rows)
+            self._probe(q, k, v, out)
             self.last_mask = mask
             self.sparsity_acc += 1.0 - density(self.mask_ratios)
             self.sparsity_counter += 1
@@ -224,6 +270,7 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
                 ev.append((e0, e1))
+        self._probe(q, k, v, out)
         self.last_mask = mask
         self.sparsity_acc += 1.0 - density(self.mask_ratios)
         self.sparsity_counter += 1

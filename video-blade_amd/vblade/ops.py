@@ -873,6 +873,84 @@ def mask_recall(q, k, block_mask, probe_pos, *, rows=None, scale=None, want_rows
 
 
 # ----------------------------------------------------------------------------------------------
+# output-fidelity probe
+# ----------------------------------------------------------------------------------------------
+FIDELITY_MAX_SAMPLES = _lib.VB_FIDELITY_MAX_SAMPLES
+FIDELITY_CHUNK = _lib.VB_FIDELITY_CHUNK
+
+
+def attn_fidelity(q, k, v, out, probe_rows, *, scale=None, want_rows: bool = False, want_ref: bool = False):
+    """vb_attn_fidelity: the error of ``out`` against exact dense attention for S <= 64 probe queries
+    per head. q, k, v, out [B,H,L,D] (strided views are read in place); ``probe_rows`` the CALLER rows
+    of the probe queries, shared by every (b,h): a device int32 [S] tensor (clamped to [0, L-1] by the
+    kernel) or a host list / numpy array, which is range-checked. Needs no mask and no order: whichever
+    module or option produced ``out``. Returns (err, sig, peak), fp32 [B,H]: the squared error and the
+    squared reference summed over the probe rows, and max |ref|; then (row_err, row_sig, row_lse), fp32
+    [B,H,S], when ``want_rows``; then ref, fp32 [B,H,S,D], when ``want_ref``."""
+    if q.dim() != 4 or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
+        raise ValueError(f"attn_fidelity: q, k, v and out must share a [B,H,L,D] shape, got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)} and {tuple(out.shape)}")
+    dev = _require_gpu(q, k, v, out)
+    if not (q.dtype == k.dtype == v.dtype == out.dtype):
+        raise TypeError(f"attn_fidelity: q, k, v and out must share a dtype, got {q.dtype}, {k.dtype}, "
+                        f"{v.dtype} and {out.dtype}")
+    B, H, L, D = q.shape
+    if isinstance(probe_rows, torch.Tensor) and probe_rows.is_cuda:
+        if probe_rows.dim() != 1:
+            raise ValueError(f"attn_fidelity: probe_rows must be one-dimensional, got {tuple(probe_rows.shape)}")
+        _check_dev("attn_fidelity: probe_rows", probe_rows, dev)
+        probe_rows = probe_rows.to(torch.int32).contiguous()
+    else:
+        r = np.asarray(probe_rows.numpy() if isinstance(probe_rows, torch.Tensor) else probe_rows)
+        if r.ndim != 1 or r.size == 0 or not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("attn_fidelity: probe_rows must be a non-empty one-dimensional list of integers")
+        if r.min() < 0 or r.max() >= L:
+            raise ValueError(f"attn_fidelity: probe_rows must lie in [0, {L}), got [{r.min()}, {r.max()}]")
+        probe_rows = torch.from_numpy(r.astype(np.int32)).to(dev)
+    S = probe_rows.numel()
+    if not 1 <= S <= FIDELITY_MAX_SAMPLES:
+        raise ValueError(f"attn_fidelity: 1 to {FIDELITY_MAX_SAMPLES} probe rows, got {S}")
+    a = _lib.FidelityArgs()
+    a.B, a.H, a.L, a.D, a.S = B, H, L, D, S
+    a.scale = float(scale) if scale else 0.0
+    a.dtype = _dtype_code(q)
+    lib = _lib.load()
+    nbytes = int(lib.vb_attn_fidelity_workspace_size(ctypes.byref(a)))
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    q, k, v, out = _aligned_bhld(q), _aligned_bhld(k), _aligned_bhld(v), _aligned_bhld(out)
+    err = torch.empty(B, H, device=dev, dtype=torch.float32)
+    sig = torch.empty(B, H, device=dev, dtype=torch.float32)
+    peak = torch.empty(B, H, device=dev, dtype=torch.float32)
+    row_err = row_sig = row_lse = ref = None
+    if want_rows:
+        row_err = torch.empty(B, H, S, device=dev, dtype=torch.float32)
+        row_sig = torch.empty(B, H, S, device=dev, dtype=torch.float32)
+        row_lse = torch.empty(B, H, S, device=dev, dtype=torch.float32)
+    if want_ref:
+        ref = torch.empty(B, H, S, D, device=dev, dtype=torch.float32)
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.q_stride, a.k_stride, a.v_stride, a.out_stride = _s3(q), _s3(k), _s3(v), _s3(out)
+    a.probe_rows = probe_rows.data_ptr()
+    a.err, a.sig, a.peak = err.data_ptr(), sig.data_ptr(), peak.data_ptr()
+    a.row_err, a.row_sig, a.row_lse, a.ref = _ptr(row_err), _ptr(row_sig), _ptr(row_lse), _ptr(ref)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    check(lib.vb_attn_fidelity(ctypes.byref(a), _stream(dev)), "vb_attn_fidelity")
+    res = (err, sig, peak)
+    if want_rows:
+        res += (row_err, row_sig, row_lse)
+    if want_ref:
+        res += (ref,)
+    return res
+
+
+def fidelity_snr_db(err: torch.Tensor, sig: torch.Tensor) -> torch.Tensor:
+    """10 log10(sig / err) per head, +inf where err == 0."""
+    e, s = err.double(), sig.double()
+    snr = 10.0 * torch.log10(s / e)
+    return torch.where(e == 0, torch.full_like(snr, float("inf")), snr)
+
+
+# ----------------------------------------------------------------------------------------------
 # mask predictor: the softmax-mass block score
 # ----------------------------------------------------------------------------------------------
 MASS_NUM_KEEP = 32   # the only sampling density vb_mask_scores_mass is built for
