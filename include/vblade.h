@@ -365,6 +365,27 @@ typedef struct vb_attn_bwd_args {
 uint64_t vb_attn_bwd_workspace_size(const vb_attn_bwd_args* args);
 int vb_attn_bwd(const vb_attn_bwd_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact backward of the ONE-softmax form vb_attn_fwd evaluates with kp/vp/kp_log_bias (the
+ * inference call, and the training forward of grad_combine="joint"). The function differentiated is
+ *   out[i] = sum_j P[i,j] v[j] + sum_m Pp[i,m] vp[m],
+ *   P[i,j]  = exp(scale q[i].k[j]            - lse[i])   over the keys j of blocks block_mask keeps,
+ *   Pp[i,m] = exp(scale q[i].kp[m] + beta    - lse[i])   over all Lkp pooled keys,
+ *   lse[i]  = log(sum_j exp(scale q[i].k[j]) + sum_m exp(scale q[i].kp[m] + beta)),
+ * with beta = pool_log_bias, the block mask a constant, and kp/vp the mean pool of k/v over
+ * `pool_gap` consecutive REORDERED keys (replicate padding onto the last key), so dk/dv receive the
+ * pooled keys' gradients folded back through that pool. The gradient is exact: one LSE and one
+ * Delta = rowsum(dO * out) serve both key sets. vb_attn_bwd's two-branch form instead holds both
+ * branch LSEs and the combine weight alpha constant (the reference's autograd), which drops the
+ * term (out1 - out2) * d alpha; dq and dk of the two therefore differ, dv does not.
+ * Same struct and conventions as vb_attn_bwd: `out` and `lse` are the joint forward's (vb_attn_fwd
+ * with need of the LSE, the same kp_log_bias); kp, vp, Lkp > 0 and pool_gap > 0 are required; out2,
+ * lse2 and alpha must be NULL. Workspace: vb_attn_bwd_workspace_size(args). kernel_select and
+ * kernels_ran keep their meaning (only the per-row statistics pass differs). No atomics: results
+ * are bit-reproducible, and a sample's gradients are the same bits alone or inside a batch.
+ * ------------------------------------------------------------------------------------------ */
+int vb_attn_bwd_joint(const vb_attn_bwd_args* args, float pool_log_bias, void* stream);
+
 /* Drop-in for the block_sparse_attn_func backward (same tensor conventions as
  * vb_block_sparse_attn_fwd): dq/dk/dv [total, H, D]; softmax_lse as the forward wrote it.
  * workspace >= vb_block_sparse_attn_bwd_workspace_size(batch, num_heads, max_seqlen_q) bytes. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of library variants (video-blade_amd/vblade/variants/lib_<tag>.so) in ONE process on
 ONE GPU: the same inputs, launches interleaved A,B,A,B,... so clock/device drift cancels.
-usage: python tools/ab.py TAG_A TAG_B [--variant cog|wan|both] [--what attn|pred|call]
+usage: python tools/ab.py TAG_A TAG_B [--variant cog|wan|both] [--what attn|pred|call|trainfwd|bwd|traincall|...]
 TAG "cur" is the in-tree libvblade_hip.so; a "@torchrand" suffix runs that tag with the sampling
 draws made by torch.rand instead of inside the sampling launch (ops.PHILOX_DRAWS off), "@lvsep"
 with the multi-level mask as its own vb_level_mask launch (--what mlcall: the multi-level module),
@@ -10,7 +10,11 @@ with the multi-level mask as its own vb_level_mask launch (--what mlcall: the mu
 "@env:VAR=VAL+VAR=VAL" with those environment variables set around its launches, "@persist" with the
 persistent (work-queue) attention launch (ops.attention_fwd persistent=True; off otherwise),
 "@sel:N" with the backward's kernel_select bits N (--what bwd / mlbwd), "@serialfwd" with the
-training forward's two branches on one stream (--what trainfwd; autograd.FORK_POOLED_BRANCH off).
+training forward's two branches on one stream (--what trainfwd; autograd.FORK_POOLED_BRANCH off),
+"@joint" with the joint training path (grad_combine="joint"): --what trainfwd times the one-launch LSE
+forward (autograd.adaptive_joint_attention), --what bwd ops.attention_bwd_joint on that forward's
+statistics, --what traincall the module's forward and backward under autograd, predictor included, on
+bench.py's inputs (it also prints each tag's peak torch.cuda.max_memory_allocated over one call).
 Compile-time switches are A/B'd as build variants (VB_EXTRA_FLAGS=-D... tools/build_variant.sh TAG)."""
 import argparse
 import ctypes
@@ -47,6 +51,7 @@ def load(tag):
 
 ORDER = [True, 0, False, 0]   # longest-first order, order window, persistent attention launch,
                              # backward kernel_select
+JOINT = [False]               # the joint training path ("@joint")
 
 
 def select(tag, libs):
@@ -56,6 +61,7 @@ def select(tag, libs):
     ORDER[1] = 0
     ORDER[2] = "@persist" in tag
     ORDER[3] = 0
+    JOINT[0] = "joint" in tag.split("@")[1:]
     for part in tag.split("@")[1:]:
         if part.startswith("win:"):
             ORDER[1] = int(part[4:])
@@ -111,8 +117,12 @@ def main():
                                            heavy_rows=m.force_tail, persistent=ORDER[2])[0]
             fl = attn_flops(mask, L, D, 0)
         elif a.what == "trainfwd":   # the training forward (two LSE branches + combine), no grad taken
-            fn = lambda: vautograd.adaptive_split_attention(q, k, v, mask, rows, m.sample_gap,  # noqa
-                                                            heavy_rows=m.force_tail)
+            def fn():
+                if JOINT[0]:   # one launch over kept and pooled keys, LSE stored (pool_kv inside, as the split's)
+                    return vautograd.adaptive_joint_attention(q, k, v, mask, rows, m.sample_gap,
+                                                              m._log_gap(q.dtype), heavy_rows=m.force_tail)
+                return vautograd.adaptive_split_attention(q, k, v, mask, rows, m.sample_gap,
+                                                          heavy_rows=m.force_tail)
             fl = attn_flops(mask, L, D, kp.shape[2])
         elif a.what == "pred":
             fn = lambda: m.predict_mask(q, k, qo, ko)  # noqa
@@ -124,10 +134,19 @@ def main():
             out2, lse2 = ops.attention_fwd(q, None, None, use_main=False, q_rows=rows, kp=kp, vp=vp,
                                            need_lse=True)
             _, alpha = ops.lse_combine(out1, lse1, out2, lse2, gap)
-            fn = lambda: ops.attention_bwd(do, q, k_r, v_r, out1, lse1, block_mask=mask, q_rows=rows,  # noqa
-                                           kv_rows=rows, kp=kp, vp=vp, out2=out2, lse2=lse2,
-                                           alpha=alpha, gap=gap, heavy_rows=m.force_tail,
-                                           kernel_select=ORDER[3])
+            beta = m._log_gap(q.dtype)
+            outj, lsej = ops.attention_fwd(q, k_r, v_r, block_mask=mask, q_rows=rows, kp=kp, vp=vp,
+                                           kp_log_bias=beta, need_lse=True, heavy_rows=m.force_tail)
+
+            def fn():
+                if JOINT[0]:   # vb_attn_bwd_joint on the one-softmax forward's statistics
+                    return ops.attention_bwd_joint(do, q, k_r, v_r, outj, lsej, block_mask=mask, q_rows=rows,
+                                                   kv_rows=rows, kp=kp, vp=vp, gap=gap, kp_log_bias=beta,
+                                                   heavy_rows=m.force_tail, kernel_select=ORDER[3])
+                return ops.attention_bwd(do, q, k_r, v_r, out1, lse1, block_mask=mask, q_rows=rows,
+                                         kv_rows=rows, kp=kp, vp=vp, out2=out2, lse2=lse2,
+                                         alpha=alpha, gap=gap, heavy_rows=m.force_tail,
+                                         kernel_select=ORDER[3])
             fl = 2.5 * fl
         elif a.what == "mlbwd":   # the multi-level path's backward (vb_ml_attn_bwd), dk compared
             do = torch.randn_like(q)
@@ -149,6 +168,17 @@ def main():
             def fn():
                 mlm.persistent = ORDER[2]
                 return mlm(q, k, v)
+        elif a.what == "traincall":   # the module under autograd: predictor, forward and backward
+            do = torch.randn_like(q)
+            qg, kg, vg = (t.clone().requires_grad_(True) for t in (q, k, v))
+
+            def fn():
+                m.grad_combine = "joint" if JOINT[0] else "reference"
+                qg.grad = kg.grad = vg.grad = None
+                with torch.enable_grad():
+                    out = m(qg, kg, vg)
+                    out.backward(do)
+                return out.detach(), qg.grad, kg.grad, vg.grad
         else:
             def fn():
                 m.order, m.order_window, m.persistent = ORDER[0], ORDER[1], ORDER[2]
@@ -158,16 +188,27 @@ def main():
         with torch.no_grad():
             for t in a.tags:   # warm + cross-check outputs (a repeated tag checks determinism)
                 select(t, libs)
-                if a.what in ("call", "mlcall"):
+                if a.what in ("call", "mlcall", "traincall"):
                     torch.cuda.manual_seed(1234)   # the module draws its sampling offsets per call
                 out = fn()
                 torch.cuda.synchronize()
+                if a.what == "traincall":   # peak memory of one forward and backward, above what is held before it
+                    out = tuple(o.clone() for o in out)
+                    qg.grad = kg.grad = vg.grad = None
+                    torch.cuda.manual_seed(1234)
+                    held = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    fn()
+                    torch.cuda.synchronize()
+                    peak = torch.cuda.max_memory_allocated()
+                    print(f"  {t}: peak memory allocated over one forward and backward {peak / 2**20:.1f} MiB "
+                          f"({(peak - held) / 2**20:.1f} MiB above the {held / 2**20:.1f} MiB held before it)")
                 if a.what == "pred":   # the same scores and energy rule: masks must be identical
                     if ref is None:
                         ref = out[1].clone()
                     else:
                         print(f"  {t}: mask identical to {a.tags[0]}: {torch.equal(out[1], ref)}")
-                if a.what in ("attn", "fwdlse", "bwd", "mlbwd", "mlattn", "trainfwd", "call", "mlcall"):
+                if a.what in ("attn", "fwdlse", "bwd", "mlbwd", "mlattn", "trainfwd", "call", "mlcall", "traincall"):
                     outs = tuple(out) if isinstance(out, tuple) else (out,)   # bwd: dq, dk, dv
                     if ref is None:
                         ref = tuple(o.clone() for o in outs)

@@ -5,6 +5,7 @@ sparse attention under autograd + gradient checkpointing, with the bucketed RCCL
 all-reduce across ranks (torchrun: one process per GPU).
 
     python tools/train_bench.py [--layers 4] [--batch 1] [--accum 1] [--steps 3] [--warmup 1]
+                                [--grad-combine reference|joint]
     python tools/train_bench.py --gpus N ...   (starts N worker processes itself, one per GPU)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/train_bench.py ...
 
@@ -70,6 +71,10 @@ def main():
     ap.add_argument("--rank-lora", type=int, default=64)
     ap.add_argument("--variant", default="cog", choices=["cog", "wan"])
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--grad-combine", default="reference", choices=["reference", "joint"],
+                    help="what the sparse attention differentiates: the reference's two-branch form (LSEs and "
+                         "alpha constants) or the one softmax the inference call evaluates, exactly "
+                         "(AdaptiveBlockSparseAttn grad_combine)")
     ap.add_argument("--tdm", action="store_true",
                     help="the two-model TDM step (student + fake-score model with sparse attention, frozen "
                          "dense teacher with CFG, two AdamW, two reducers; train_cogvideo_tdm.py:1301-1325, "
@@ -96,7 +101,7 @@ def main():
     from vblade import train as T
     heads, D = (48, 64) if args.variant == "cog" else (12, 128)
     hidden = heads * D
-    attn = vblade.AdaptiveBlockSparseAttn(args.variant, log_every=0)
+    attn = vblade.AdaptiveBlockSparseAttn(args.variant, log_every=0, grad_combine=args.grad_combine)
     timed = TimedAttention(attn)
     L = attn.gilbert_rearranger.seq_len
     model = T.StandInTransformer(args.layers, hidden, heads, args.rank_lora, float(args.rank_lora), timed,
@@ -153,7 +158,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "dtype": "bf16", "data": "synthetic",
             "config": {"layers": args.layers, "micro_batch": args.batch, "accum": args.accum, "seq_len": L,
                        "heads": heads, "head_dim": D, "lora_rank": args.rank_lora,
-                       "gradient_checkpointing": True,
+                       "gradient_checkpointing": True, "grad_combine": args.grad_combine,
                        "parallelism": f"dp{world} (bucketed RCCL all-reduce of LoRA grads)"},
             "attention_fwd_ms_per_step": round(fwd_ms / args.steps, 2),
             "attention_bwd_ms_per_step": round(bwd_ms / args.steps, 2),

@@ -16,7 +16,9 @@
 //   bwd_prep_kernel   per row: -Delta1/2, L'1/2 -> stats [B*H][ntile64][4][64] fp32 (Delta negated:
 //                     it seeds the dP accumulators, see below); optional
 //                     reordered contiguous copies of q and dO (one gather pass instead of one per
-//                     key block that reads them)
+//                     key block that reads them). Its kJoint form (vb_attn_bwd_joint) writes the
+//                     statistics of the exact gradient of the one-softmax function instead: one
+//                     LSE and one Delta, L'2 = (lse - beta) log2e; the kernels below are the same
 //   bwd_dkdv_kernel   one workgroup per (b, h, 128-key block); wave = 32 keys held in registers;
 //                     streams the 64-row Q / dO tiles of every q-block that keeps this key block
 //                     (mask column; all q-blocks for pooled keys) through LDS by LDS-DMA:
@@ -41,7 +43,12 @@ namespace vb {
 // ------------------------------------------------------------------------------------------------
 // prep: one thread per 16-byte chunk of a row
 // ------------------------------------------------------------------------------------------------
-template <class T>
+// kJoint (vb_attn_bwd_joint): out / lse belong to one softmax over the kept keys and the pooled keys
+// with the logit bias beta = pool_log_bias. Its exact gradient has one Delta = rowsum(dO * O) for both
+// key sets, P = exp(S c - lse) on the kept keys and P = exp(S c + beta - lse) on the pooled ones,
+// whose scores carry no bias in the gradient kernels: L'2 = (lse - beta) log2e. out2, lse2 and alpha
+// are never read.
+template <class T, bool kJoint = false>
 __global__ void __launch_bounds__(256) bwd_prep_kernel(const PrepParams p) {
   const int CH = p.D / 8;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,7 +72,7 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(const PrepParams p) {
     const u32x4 ov = *reinterpret_cast<const u32x4*>(
         reinterpret_cast<const uint8_t*>(p.out) + 2 * (b * p.os[0] + h * p.os[1] + r * p.os[2] + ch * 8));
     u32x4 o2v = {0, 0, 0, 0};
-    if (p.out2)
+    if (!kJoint && p.out2)
       o2v = *reinterpret_cast<const u32x4*>(
           reinterpret_cast<const uint8_t*>(p.out2) + 2 * (b * p.o2s[0] + h * p.o2s[1] + r * p.o2s[2] + ch * 8));
 #pragma unroll
@@ -74,7 +81,7 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(const PrepParams p) {
       for (int s = 0; s < 2; ++s) {
         const float x = T::bits_to_f32((dov[e] >> (16 * s)) & 0xffff);
         d1 += x * T::bits_to_f32((ov[e] >> (16 * s)) & 0xffff);
-        d2 += x * T::bits_to_f32((o2v[e] >> (16 * s)) & 0xffff);
+        if (!kJoint) d2 += x * T::bits_to_f32((o2v[e] >> (16 * s)) & 0xffff);
       }
     if (p.q_r) {
       const u32x4 qv = *reinterpret_cast<const u32x4*>(
@@ -87,21 +94,30 @@ __global__ void __launch_bounds__(256) bwd_prep_kernel(const PrepParams p) {
   // reduce over the CH consecutive lanes of this row (CH in {8, 16}, aligned groups)
   for (int o = 1; o < CH; o <<= 1) {
     d1 += __shfl_xor(d1, o);
-    d2 += __shfl_xor(d2, o);
+    if (!kJoint) d2 += __shfl_xor(d2, o);
   }
   if (ch != 0) return;
   float l1 = bwd::kBigL, l2 = bwd::kBigL;
   if (valid) {
     const int64_t li = (int64_t)bh * p.Lq + row;
-    const float a = p.alpha ? p.alpha[li] : 1.f;
     const float lse1 = p.lse[li];
-    // a * P1 = exp2(S c - (lse1 log2e - log2 a)); rows with no kept key (lse = -inf) or a = 0
-    // contribute nothing
-    if (lse1 > -INFINITY && a > 0.f) l1 = fminf(lse1 * kLog2e - __log2f(a), bwd::kBigL);
-    if (p.lse2) {
-      const float w2 = round_to<T>(1.f - a);  // the reference's bf16 (1 - alpha), :393
-      const float lse2 = p.lse2[li];
-      if (lse2 > -INFINITY && w2 > 0.f) l2 = fminf(lse2 * kLog2e - __log2f(w2), bwd::kBigL);
+    if (kJoint) {
+      // one LSE and one Delta for both key sets; the pooled scores get their bias through L'2
+      if (lse1 > -INFINITY) {
+        l1 = fminf(lse1 * kLog2e, bwd::kBigL);
+        l2 = fminf((lse1 - p.pool_log_bias) * kLog2e, bwd::kBigL);
+      }
+      d2 = d1;
+    } else {
+      const float a = p.alpha ? p.alpha[li] : 1.f;
+      // a * P1 = exp2(S c - (lse1 log2e - log2 a)); rows with no kept key (lse = -inf) or a = 0
+      // contribute nothing
+      if (lse1 > -INFINITY && a > 0.f) l1 = fminf(lse1 * kLog2e - __log2f(a), bwd::kBigL);
+      if (p.lse2) {
+        const float w2 = round_to<T>(1.f - a);  // the reference's bf16 (1 - alpha), :393
+        const float lse2 = p.lse2[li];
+        if (lse2 > -INFINITY && w2 > 0.f) l2 = fminf(lse2 * kLog2e - __log2f(w2), bwd::kBigL);
+      }
     }
   } else {
     d1 = d2 = 0.f;
@@ -941,10 +957,13 @@ __global__ void __launch_bounds__(256) pool_grad_reduce_kernel(const float* pk, 
 // ------------------------------------------------------------------------------------------------
 // launchers (vb_attn_bwd.hpp); the host layer is vb_attn_bwd_host.cpp
 // ------------------------------------------------------------------------------------------------
-int launch_prep(const PrepParams& pp, int dtype, hipStream_t s) {
+int launch_prep(const PrepParams& pp, int dtype, bool joint, hipStream_t s) {
   const int64_t threads = (int64_t)pp.B * pp.H * pp.ntile * 64 * (pp.D / 8);
   const dim3 grid((unsigned)((threads + 255) / 256));
-  if (dtype == VB_DTYPE_BF16) hipLaunchKernelGGL(bwd_prep_kernel<BF16>, grid, dim3(256), 0, s, pp);
+  if (joint) {
+    if (dtype == VB_DTYPE_BF16) hipLaunchKernelGGL((bwd_prep_kernel<BF16, true>), grid, dim3(256), 0, s, pp);
+    else hipLaunchKernelGGL((bwd_prep_kernel<F16, true>), grid, dim3(256), 0, s, pp);
+  } else if (dtype == VB_DTYPE_BF16) hipLaunchKernelGGL(bwd_prep_kernel<BF16>, grid, dim3(256), 0, s, pp);
   else hipLaunchKernelGGL(bwd_prep_kernel<F16>, grid, dim3(256), 0, s, pp);
   return check_launch("bwd_prep_kernel");
 }

@@ -45,6 +45,9 @@ struct PrepParams {
   void* q_r; void* do_r;  // [B,H,Lq,D] contiguous reordered copies (written when q_rows != NULL)
   float* stats;           // [B*H][ntile][4][64]: L'1, -Delta1, L'2, -Delta2
   int B, H, Lq, D, ntile;
+  // vb_attn_bwd_joint: out / lse are those of the ONE softmax over kept keys and biased pooled keys,
+  // pool_log_bias its bias (out2, lse2 and alpha are NULL and never read)
+  float pool_log_bias;
 };
 
 struct BwdParams {
@@ -144,7 +147,8 @@ __device__ __forceinline__ void dq_item(const BwdParams& p, int BH, int& bh, int
 
 // ---- launchers: each returns 0 or a VB_ERR code; dtype is VB_DTYPE_BF16 / VB_DTYPE_F16 -------------
 // vb_attn_bwd.hip (compiler-scheduled)
-int launch_prep(const PrepParams& pp, int dtype, hipStream_t s);
+// joint: the statistics of vb_attn_bwd_joint (PrepParams::pool_log_bias) instead of the two-branch ones
+int launch_prep(const PrepParams& pp, int dtype, bool joint, hipStream_t s);
 // the round-3 dK/dV: pooled-key pass (grid nbkp * B*H * psplit) or full-resolution (grid nbk * B*H)
 int launch_dkdv_round3(const BwdParams& p, int D, int dtype, bool pooled, hipStream_t s);
 // the multi-level level-1 dK/dV on the round-3 kernel

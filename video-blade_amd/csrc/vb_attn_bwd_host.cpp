@@ -1,5 +1,5 @@
 // Host layer of the block-sparse FMHA backward: argument validation, workspace layout, parameter
-// fill and launch sequencing of vb_attn_bwd, vb_block_sparse_attn_bwd and vb_ml_attn_bwd. The
+// fill and launch sequencing of vb_attn_bwd, vb_attn_bwd_joint, vb_block_sparse_attn_bwd and vb_ml_attn_bwd. The
 // kernels and their launchers are in vb_attn_bwd.hip (compiler-scheduled) and vb_attn_bwd_kv.hip
 // (hand-placed streams); nothing here is compiled with their per-file flags.
 #include <map>
@@ -174,9 +174,10 @@ int launch_dkdv(const BwdParams& p, int D, int dtype, bool pooled, bool pipe, hi
   return pipe ? launch_dkdv_pipe(p, D, dtype, pooled, s) : launch_dkdv_round3(p, D, dtype, pooled, s);
 }
 
+// joint: the prep launch writes vb_attn_bwd_joint's statistics; the gradient launches are the same
 int launch_grads(const PrepParams& pp, const BwdParams& p, int D, int dtype, bool pool, hipStream_t s, int sel,
-                 int& ran) {
-  if (int rc = launch_prep(pp, dtype, s)) return rc;
+                 int& ran, bool joint = false) {
+  if (int rc = launch_prep(pp, dtype, joint, s)) return rc;
   const bool pipe = !(sel & VB_BWD_SEL_DKDV_ROUND3);
   if ((pool && p.dkp) || p.k) ran |= pipe ? VB_BWD_RAN_DKDV_PIPE : VB_BWD_RAN_DKDV_ROUND3;
   ForkScope fork(s, D == 128);
@@ -193,7 +194,7 @@ int launch_grads(const PrepParams& pp, const BwdParams& p, int D, int dtype, boo
 }
 
 int launch_ml_grads(const PrepParams& pp, const BwdParams& p, int D, int dtype, hipStream_t s, int sel, int& ran) {
-  if (int rc = launch_prep(pp, dtype, s)) return rc;
+  if (int rc = launch_prep(pp, dtype, false, s)) return rc;
   ran |= VB_BWD_RAN_ML_PYRAMID;
   // dQ stays last on the caller's stream: forked beside the pyramid and level-1 passes it measured
   // 0.987-0.990x (ForkScope)
@@ -221,45 +222,53 @@ extern "C" uint64_t vb_attn_bwd_workspace_size(const vb_attn_bwd_args* a) {
   return vb::ws_layout(a->B, a->H, a->Lq, a->D, a->q_rows != nullptr, a->kp ? a->Lkp : 0).total;
 }
 
-extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
-  using namespace vb;
-  if (!a) return fail(VB_ERR_INVALID, "vb_attn_bwd: null args");
+namespace vb {
+namespace {
+// vb_attn_bwd (joint = false) and vb_attn_bwd_joint: `entry` names the call in the messages
+int attn_bwd(const vb_attn_bwd_args* a, bool joint, float pool_log_bias, void* stream, const std::string& entry) {
+  if (!a) return fail(VB_ERR_INVALID, entry + ": null args");
   if (a->B <= 0 || a->H <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->D <= 0)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: B, H, Lq, Lk, D must be positive");
+    return fail(VB_ERR_INVALID, entry + ": B, H, Lq, Lk, D must be positive");
   if (!head_dim_ok(a->D))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: head_dim must be 64 or 128, got " + std::to_string(a->D));
-  if (!dtype_ok(a->dtype)) return fail(VB_ERR_INVALID, "vb_attn_bwd: unknown dtype");
+    return fail(VB_ERR_UNSUPPORTED, entry + ": head_dim must be 64 or 128, got " + std::to_string(a->D));
+  if (!dtype_ok(a->dtype)) return fail(VB_ERR_INVALID, entry + ": unknown dtype");
   if (!a->q || !a->k || !a->v || !a->out || !a->lse || !a->dout || !a->dq || !a->dk || !a->dv)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: missing tensor");
+    return fail(VB_ERR_INVALID, entry + ": missing tensor");
   if (a->kernel_select & ~(VB_BWD_SEL_DKDV_ROUND3 | VB_BWD_SEL_DQ_ROUND3 | VB_BWD_SEL_DQ_RING4))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: unknown kernel_select bits");
+    return fail(VB_ERR_INVALID, entry + ": unknown kernel_select bits");
   const bool pool = a->kp != nullptr;
-  if (pool && (!a->vp || a->Lkp <= 0 || !a->out2 || !a->lse2 || a->pool_gap <= 0))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: pooled branch needs vp, Lkp, out2, lse2 and pool_gap");
+  if (joint) {
+    if (!pool || !a->vp || a->Lkp <= 0 || a->pool_gap <= 0)
+      return fail(VB_ERR_INVALID, entry + ": needs the pooled keys kp, vp, Lkp > 0 and pool_gap > 0");
+    if (a->out2 || a->lse2 || a->alpha)
+      return fail(VB_ERR_INVALID, entry + ": out2, lse2 and alpha must be NULL (one softmax has one output and one LSE)");
+  } else if (pool && (!a->vp || a->Lkp <= 0 || !a->out2 || !a->lse2 || a->pool_gap <= 0))
+    return fail(VB_ERR_INVALID, entry + ": pooled branch needs vp, Lkp, out2, lse2 and pool_gap");
   if (pool && (int64_t)a->Lkp * a->pool_gap < a->Lk)
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: Lkp * pool_gap must cover Lk");
+    return fail(VB_ERR_INVALID, entry + ": Lkp * pool_gap must cover Lk");
   const int nbk = (a->Lk + 127) / 128;
   const int nbq = (a->Lq + 127) / 128;
-  if (nbk > bwd::kMaxBlocks || nbq > bwd::kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: sequence too long");
+  if (nbk > bwd::kMaxBlocks || nbq > bwd::kMaxBlocks) return fail(VB_ERR_UNSUPPORTED, entry + ": sequence too long");
   const int64_t* strides[] = {a->q_stride, a->k_stride, a->v_stride, a->out_stride, a->dout_stride,
                               a->dq_stride, a->dk_stride, a->dv_stride};
   for (const int64_t* s : strides)
-    if (!strides_mul8(s)) return fail(VB_ERR_INVALID, "vb_attn_bwd: strides must be multiples of 8 elements");
-  if (pool && (!strides_mul8(a->kp_stride) || !strides_mul8(a->vp_stride) || !strides_mul8(a->out2_stride)))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: strides must be multiples of 8 elements");
+    if (!strides_mul8(s)) return fail(VB_ERR_INVALID, entry + ": strides must be multiples of 8 elements");
+  if (pool && (!strides_mul8(a->kp_stride) || !strides_mul8(a->vp_stride) ||
+               (!joint && !strides_mul8(a->out2_stride))))
+    return fail(VB_ERR_INVALID, entry + ": strides must be multiples of 8 elements");
   const void* ptrs[] = {a->q, a->k, a->v, a->out, a->dout, a->dq, a->dk, a->dv};
   for (const void* q : ptrs)
-    if (!aligned16(q)) return fail(VB_ERR_INVALID, "vb_attn_bwd: tensors must be 16-byte aligned");
+    if (!aligned16(q)) return fail(VB_ERR_INVALID, entry + ": tensors must be 16-byte aligned");
   if (pool && (!aligned16(a->kp) || !aligned16(a->vp) || !aligned16(a->out2)))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: tensors must be 16-byte aligned");
+    return fail(VB_ERR_INVALID, entry + ": tensors must be 16-byte aligned");
   const WsLayout w = ws_layout(a->B, a->H, a->Lq, a->D, a->q_rows != nullptr, pool ? a->Lkp : 0);
   if (!a->workspace || a->workspace_bytes < w.total || !aligned16(a->workspace))
-    return fail(VB_ERR_INVALID, "vb_attn_bwd: workspace missing or smaller than vb_attn_bwd_workspace_size()");
+    return fail(VB_ERR_INVALID, entry + ": workspace missing or smaller than vb_attn_bwd_workspace_size()");
   if (!a->q_rows && (!slice_fits32(a->Lq, a->q_stride[2], a->D) || !slice_fits32(a->Lq, a->dout_stride[2], a->D)))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: a q/dout (b,h) slice spans >= 2 GiB");
+    return fail(VB_ERR_UNSUPPORTED, entry + ": a q/dout (b,h) slice spans >= 2 GiB");
   if (!slice_fits32(a->Lk, a->k_stride[2], a->D) || !slice_fits32(a->Lk, a->v_stride[2], a->D) ||
       (pool && (!slice_fits32(a->Lkp, a->kp_stride[2], a->D) || !slice_fits32(a->Lkp, a->vp_stride[2], a->D))))
-    return fail(VB_ERR_UNSUPPORTED, "vb_attn_bwd: a k/v/kp/vp (b,h) slice spans >= 2 GiB");
+    return fail(VB_ERR_UNSUPPORTED, entry + ": a k/v/kp/vp (b,h) slice spans >= 2 GiB");
   uint8_t* ws = reinterpret_cast<uint8_t*>(a->workspace);
 
   PrepParams pp{};
@@ -267,6 +276,7 @@ extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
   fill_q_side(pp, p, ws, w, a->q, a->q_stride, a->dout, a->dout_stride, a->q_rows, a->B, a->H, a->Lq, a->D);
   pp.out = a->out; copy3(pp.os, a->out_stride);
   pp.lse = a->lse; pp.alpha = a->alpha;
+  pp.pool_log_bias = pool_log_bias;
   p.k = a->k; p.v = a->v;
   copy3(p.ks, a->k_stride); copy3(p.vs, a->v_stride);
   copy3(p.ms, a->mask_stride);
@@ -276,8 +286,10 @@ extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
   p.psplit = 1;
   p.gap = 1;
   if (pool) {
-    pp.out2 = a->out2; copy3(pp.o2s, a->out2_stride);
-    pp.lse2 = a->lse2;
+    if (!joint) {
+      pp.out2 = a->out2; copy3(pp.o2s, a->out2_stride);
+      pp.lse2 = a->lse2;
+    }
     p.kp = a->kp; p.vp = a->vp; p.Lkp = a->Lkp;
     copy3(p.kps, a->kp_stride); copy3(p.vps, a->vp_stride);
     p.dkp = reinterpret_cast<float*>(ws + w.dkp); p.dvp = reinterpret_cast<float*>(ws + w.dvp);
@@ -290,9 +302,20 @@ extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
   fill_scale(p, a->scale, a->D);
   p.heavy_rows = a->heavy_rows;
   int ran = 0;
-  const int rc = launch_grads(pp, p, a->D, a->dtype, pool, reinterpret_cast<hipStream_t>(stream), a->kernel_select, ran);
+  const int rc = launch_grads(pp, p, a->D, a->dtype, pool, reinterpret_cast<hipStream_t>(stream), a->kernel_select, ran,
+                              joint);
   if (a->kernels_ran) *a->kernels_ran = ran;
   return rc;
+}
+}  // namespace
+}  // namespace vb
+
+extern "C" int vb_attn_bwd(const vb_attn_bwd_args* a, void* stream) {
+  return vb::attn_bwd(a, false, 0.f, stream, "vb_attn_bwd");
+}
+
+extern "C" int vb_attn_bwd_joint(const vb_attn_bwd_args* a, float pool_log_bias, void* stream) {
+  return vb::attn_bwd(a, true, pool_log_bias, stream, "vb_attn_bwd_joint");
 }
 
 extern "C" uint64_t vb_block_sparse_attn_bwd_workspace_size(int batch, int num_heads, int max_seqlen_q) {

@@ -12,7 +12,12 @@ from .attention import (  # noqa: F401
     draw_sample_offsets,
     retain_counts,
 )
-from .autograd import adaptive_split_attention, block_sparse_attn_func, qk_prologue  # noqa: F401
+from .autograd import (  # noqa: F401
+    adaptive_joint_attention,
+    adaptive_split_attention,
+    block_sparse_attn_func,
+    qk_prologue,
+)
 from .patch import (  # noqa: F401
     CogVideoXBlockSparseAttnProcessor,
     WanBlockSparseAttnProcessor,

@@ -290,6 +290,7 @@ SIGNATURES = {
         ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "vb_attn_bwd_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(BwdArgs)]),
     "vb_attn_bwd": (ctypes.c_int, [ctypes.POINTER(BwdArgs), _vp]),
+    "vb_attn_bwd_joint": (ctypes.c_int, [ctypes.POINTER(BwdArgs), ctypes.c_float, _vp]),
     "vb_block_sparse_attn_bwd_workspace_size": (ctypes.c_uint64, [ctypes.c_int] * 3),
     "vb_block_sparse_attn_bwd": (ctypes.c_int, [
         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -14,7 +14,10 @@ cogvideo_blocksparseattn.py:398-427; wanx_blocksparseattn.py:375-409) and its he
                           the reference's two attention calls + LSE combine, fused; q/k/v rows
                           gathered and out rows scattered through the Gilbert index (no copies)
   training (grad required) keeps the reference's two-branch structure so the backward has the
-  reference's semantics (LSE/alpha detached): see ``autograd.adaptive_split_attention``.
+  reference's semantics (LSE/alpha detached): see ``autograd.adaptive_split_attention``. With
+  grad_combine="joint" the call under autograd is the inference call (steps 1 and 2, the LSE
+  stored) and the backward is the exact gradient of that one softmax:
+  ``autograd.adaptive_joint_attention``.
 
 Only the tiny RNG draw of the sampling offsets (torch.rand + topk over [B,H,1,128], exactly as
 cogvideo_blocksparseattn.py:45-46 so the RNG stream matches the reference) stays in PyTorch.
@@ -167,7 +170,13 @@ class AdaptiveBlockSparseAttn(nn.Module):
     reference's) or 64: a quarter / four times the predictor's score work. Given q_off/k_off must
     be [B,H,num_keep].
     combine: "fused" (one softmax, inference default) or "reference" (two attention calls + the
-    reference's bf16 LSE combine, bit-for-bit structure of :366-393; always used under autograd).
+    reference's bf16 LSE combine, bit-for-bit structure of :366-393; used under autograd unless grad_combine="joint").
+    grad_combine: what a call that records gradients differentiates: "reference" (default: the two-branch
+    form above, both LSEs and the combine weight constants, the reference's gradient) or "joint" (the
+    one softmax the inference call evaluates, with the same rounded ln(gap) bias, and its exact
+    gradient: one attention launch forward, the pooled pass riding in the predictor's launch as at
+    inference, ops.attention_bwd_joint backward; dq and dk differ from the reference's by the dropped
+    (out1 - out2)·d alpha term). Inference calls are the same in both.
     mask_head_mode: how the reference's head_mask_type = ones(H) (:313) reads the predicted
     [B,H,nb,nb] mask, which SURVEY Appendix B leaves open offline: "per_head" (default: each head
     its own predicted mask, Block-Sparse-Attention's renumbering of the ones) or "shared_head0"
@@ -227,12 +236,16 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                                "mask_head_mode", "order", "order_window", "persistent",
                                                "mask_mode", "init_k", "head_budget", "judge_samples",
                                                "judge_key_stride", "judge_top", "judge_clamp", "judge_seed",
-                                               "probe", "probe_samples", "probe_seed", "probe_every", "score"}
+                                               "probe", "probe_samples", "probe_seed", "probe_every", "score",
+                                               "grad_combine"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
         self.variant = variant
         self.combine = combine
+        self.grad_combine = cfg.get("grad_combine", "reference")
+        if self.grad_combine not in ("reference", "joint"):
+            raise ValueError(f"grad_combine must be 'reference' or 'joint', got {self.grad_combine!r}")
         self.use_rearrange = cfg["use_rearrange"]
         self.max_retain_ratio = cfg["max_retain_ratio"]
         self.min_retain_ratio = cfg["min_retain_ratio"]
@@ -604,6 +617,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
         count = self._count_slot(q.device)
         grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
         fused = not grad and self.combine != "reference"
+        # grad_combine="joint": the inference call under autograd (one softmax, its exact gradient)
+        joint = grad and self.grad_combine == "joint"
         pooled = None
         rows_kept = None
         if block_mask is None:
@@ -611,9 +626,10 @@ class AdaptiveBlockSparseAttn(nn.Module):
             # contiguous copies the attention kernel streams by LDS-DMA; HBM-bound) runs inside the
             # predictor's score-kernel launch, beside the MFMA-bound score workgroups (overlap=True),
             # or after it (overlap=False)
-            ride = fused and self.overlap and self.score == "max"
+            ride = (fused or joint) and self.overlap and self.score == "max"
             gather = self._gather(D)
-            copies = not (gather and rows is not None)
+            # the joint backward reads k/v in reordered order: its copies are always taken
+            copies = joint or not (gather and rows is not None)
             outs = ops.pool_kv_outputs(k, self.sample_gap, reordered=copies) if ride else None
             if fused and self.order and self.mask_head_mode == "per_head":
                 rows_kept = torch.empty(B, H, nb, device=q.device, dtype=torch.int32)
@@ -623,12 +639,14 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                             rows_kept=rows_kept, judge_rows=judge_rows)
             if ride:
                 pooled = outs
-            elif fused:
+            elif fused or joint:
                 pooled = ops.pool_kv(k, v, self.sample_gap, rows, reordered=copies)
         else:
             mask = block_mask.to(torch.uint8)
             count.add_(mask.sum())
-            if fused:
+            if joint:
+                pooled = ops.pool_kv(k, v, self.sample_gap, rows, reordered=True)
+            elif fused:
                 gather = self._gather(D)
                 pooled = ops.pool_kv(k, v, self.sample_gap, rows, reordered=not (gather and rows is not None))
         self._slot_totals.append(B * H * nb * nb)
@@ -644,7 +662,11 @@ class AdaptiveBlockSparseAttn(nn.Module):
             if probing and "recall" in self._probes:
                 self._probe_recall(q, k, mask, rows)
             self._probe_calls += 1
-        if not fused:
+        if joint:
+            from .autograd import adaptive_joint_attention
+            out = adaptive_joint_attention(q, k, v, mask, rows, self.sample_gap, self._log_gap(q.dtype),
+                                           heavy_rows=self.force_tail, pooled=pooled)
+        elif not fused:
             from .autograd import adaptive_split_attention
             out = adaptive_split_attention(q, k, v, mask, rows, self.sample_gap,
                                            heavy_rows=self.force_tail)

@@ -7,6 +7,10 @@
   sparse branch + pooled dense branch + bf16 LSE combine. Under autograd alpha is a constant
   (both LSEs are detached), so dO1 = alpha*dO, dO2 = (1-alpha)*dO and each branch back-propagates
   with its own output and LSE; pooled-branch K/V gradients flow back through the mean pool.
+* ``adaptive_joint_attention`` — the one-softmax form the inference call evaluates, with its exact
+  gradient (nothing held constant but the block mask): one attention launch forward, one
+  ``ops.attention_bwd_joint`` call backward. Opt-in (``grad_combine="joint"``); it is not the
+  reference's gradient, which drops the term (out1 - out2)·d alpha.
 """
 from __future__ import annotations
 
@@ -116,6 +120,42 @@ class _AdaptiveSplitFn(torch.autograd.Function):
 def adaptive_split_attention(q, k, v, mask, rows, gap, heavy_rows=2):
     """heavy_rows: forced-dense tail rows dispatched first (CogVideoX 2, Wan 0); scheduling only."""
     return _AdaptiveSplitFn.apply(q, k, v, mask, rows, gap, heavy_rows)
+
+
+class _AdaptiveJointFn(torch.autograd.Function):
+    """The inference call under autograd: ONE attention launch (kept keys ∪ biased pooled keys, LSE
+    stored) forward, ops.attention_bwd_joint backward. k_r/v_r/kp/vp come from the detached k/v; the
+    backward folds the pooled keys' gradients through the mean pool and scatters to the caller's rows."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled):
+        kp, vp, k_r, v_r = pooled if pooled is not None else ops.pool_kv(k, v, gap, rows, reordered=True)
+        out, lse = ops.attention_fwd(q, k_r, v_r, block_mask=mask, q_rows=rows, kp=kp, vp=vp,
+                                     kp_log_bias=kp_log_bias, need_lse=True, heavy_rows=heavy_rows,
+                                     persistent=q.shape[-1] == 128)
+        ctx.save_for_backward(q, k_r, v_r, kp, vp, out, lse, mask, rows)
+        ctx.gap = gap
+        ctx.kp_log_bias = kp_log_bias
+        ctx.heavy_rows = heavy_rows
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k_r, v_r, kp, vp, out, lse, mask, rows = ctx.saved_tensors
+        dq, dk, dv = ops.attention_bwd_joint(dout.contiguous(), q, k_r, v_r, out, lse, block_mask=mask,
+                                             q_rows=rows, kv_rows=rows, kp=kp, vp=vp, gap=ctx.gap,
+                                             kp_log_bias=ctx.kp_log_bias, heavy_rows=ctx.heavy_rows)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def adaptive_joint_attention(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows=2, pooled=None):
+    """The one-softmax form the inference call evaluates (block-masked keys ∪ pooled keys with the
+    logit bias ``kp_log_bias``), differentiable in q, k, v with its exact gradient: the mask is a
+    constant, the pooled keys are the mean pool of the reordered k/v. ``pooled``: (kp, vp, k_r, v_r)
+    already computed from the detached k/v (ops.pool_kv(..., reordered=True), or the predictor's
+    pool= outputs), or None to run ops.pool_kv here. One attention launch forward, one
+    ops.attention_bwd_joint call backward; saves q, k_r, v_r, kp, vp, out, lse, mask, rows."""
+    return _AdaptiveJointFn.apply(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled)
 
 
 class _QkPrologueFn(torch.autograd.Function):

@@ -264,6 +264,29 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
     receives the _lib.VB_BWD_RAN_* bits of the kernels the call launched; ``workspace_bytes`` (a
     list) the size vb_attn_bwd_workspace_size reported for the call (it holds psplit copies of the
     pooled-key partials, so tests read the pooled-key split from it)."""
+    return _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2, alpha, gap,
+                          scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, None)
+
+
+def attention_bwd_joint(dout, q, k, v, out, lse, *, block_mask, q_rows, kv_rows, kp, vp, gap: int,
+                        kp_log_bias: float, scale: Optional[float] = None, heavy_rows: int = 0,
+                        dk_rows: Optional[int] = None, kernel_select: int = 0,
+                        kernels_ran: Optional[list] = None, workspace_bytes: Optional[list] = None):
+    """vb_attn_bwd_joint: the exact gradients (dq, dk, dv) of the one softmax attention_fwd evaluates
+    with kp/vp/kp_log_bias: ``out`` and ``lse`` are that call's (need_lse=True, the same kp_log_bias),
+    the block mask is a constant, and kp/vp are the mean pool of the reordered k/v over ``gap`` keys, so
+    the pooled keys' gradients are folded back into dk/dv. Unlike attention_bwd's two-branch form no
+    LSE or combine weight is held constant. The other arguments as attention_bwd."""
+    if kp is None or vp is None:
+        raise ValueError("attention_bwd_joint: the joint softmax needs the pooled keys kp and vp")
+    return _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, None, None, None, gap,
+                          scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes,
+                          float(kp_log_bias))
+
+
+def _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2, alpha, gap,
+                   scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, joint_bias):
+    """attention_bwd (``joint_bias`` None) and attention_bwd_joint (the pooled keys' logit bias)."""
     dev = _require_gpu(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2,
                        alpha)
     q, k, v, out, dout = (_aligned_bhld(t) for t in (q, k, v, out, dout))
@@ -285,13 +308,15 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
     lse = lse.float().contiguous()
     a.lse = lse.data_ptr()
     if kp is not None:
-        kp, vp, out2 = _aligned_bhld(kp), _aligned_bhld(vp), _aligned_bhld(out2)
-        lse2 = lse2.float().contiguous()
-        alpha = alpha.float().contiguous()
+        kp, vp = _aligned_bhld(kp), _aligned_bhld(vp)
         a.kp, a.vp, a.kp_stride, a.vp_stride = kp.data_ptr(), vp.data_ptr(), _s3(kp), _s3(vp)
         a.Lkp = kp.shape[2]
-        a.out2, a.out2_stride = out2.data_ptr(), _s3(out2)
-        a.lse2, a.alpha = lse2.data_ptr(), alpha.data_ptr()
+        if joint_bias is None:
+            out2 = _aligned_bhld(out2)
+            lse2 = lse2.float().contiguous()
+            alpha = alpha.float().contiguous()
+            a.out2, a.out2_stride = out2.data_ptr(), _s3(out2)
+            a.lse2, a.alpha = lse2.data_ptr(), alpha.data_ptr()
         a.pool_gap = int(gap)
     a.dout, a.dout_stride = dout.data_ptr(), _s3(dout)
     a.dq, a.dq_stride = dq.data_ptr(), _s3(dq)
@@ -309,7 +334,10 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
         workspace_bytes.append(nbytes)
     ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-    check(lib.vb_attn_bwd(ctypes.byref(a), _stream(dev)), "vb_attn_bwd")
+    if joint_bias is None:
+        check(lib.vb_attn_bwd(ctypes.byref(a), _stream(dev)), "vb_attn_bwd")
+    else:
+        check(lib.vb_attn_bwd_joint(ctypes.byref(a), joint_bias, _stream(dev)), "vb_attn_bwd_joint")
     if kernels_ran is not None:
         kernels_ran.append(ran.value)
     return dq, dk, dv
