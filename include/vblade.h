@@ -304,6 +304,23 @@ int vb_lse_combine(const void* out1, const float* lse1, const void* out2, const 
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * vb_lse_combine on strided tensors: the same arithmetic, element for element and with the same
+ * rounding points, so out and alpha are the bits vb_lse_combine writes on contiguous copies of the
+ * inputs. out1, out2 and out are each [B,H,L,D] addressed through three element strides (batch,
+ * head, row; unit d-stride; non-negative multiples of 8; bases 16-byte aligned), e.g. the
+ * [B,H,L,D] view of [B,L,H*D] projection-layout memory. lse1, lse2 and alpha (nullable) stay
+ * contiguous fp32 [B,H,L]. D is 64 or 128; B and H at most 65535 (grid dimensions). out may not
+ * overlap out1 or out2, and its rows must be distinct (no zero stride over an extent above 1).
+ * Null arguments, bad sizes, an unknown dtype, bad strides or alignment: VB_ERR_INVALID before any
+ * launch. Allocates nothing, never synchronises; one launch on `stream` (16 bytes per lane, a wave
+ * covers whole rows: a row's D*2 contiguous bytes move as full cache lines at any row stride).
+ * ------------------------------------------------------------------------------------------ */
+int vb_lse_combine_strided(const void* out1, const int64_t* out1_stride, const float* lse1,
+                           const void* out2, const int64_t* out2_stride, const float* lse2,
+                           int B, int H, int L, int D, float gap, int dtype, void* out,
+                           const int64_t* out_stride, float* alpha, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward (FlashAttention-2 semantics, deterministic: no atomics) of the block-sparse attention
  * and of the adaptive module's two-branch form, as the reference's autograd computes it
  * (cogvideo_blocksparseattn.py:316-320 + :366-393):

@@ -310,6 +310,9 @@ SIGNATURES = {
     "vb_lse_combine": (ctypes.c_int, [
         _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ctypes.c_float, ctypes.c_int, _vp, _vp, _vp]),
+    "vb_lse_combine_strided": (ctypes.c_int, [
+        _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "vb_qk_prologue": (ctypes.c_int, [ctypes.POINTER(QkPrologueArgs), ctypes.POINTER(QkPrologueArgs), _vp]),
     "vb_qk_prologue_bwd_workspace_size": (ctypes.c_uint64, [ctypes.POINTER(QkPrologueBwdArgs),
                                                             ctypes.POINTER(QkPrologueBwdArgs)]),

@@ -225,6 +225,13 @@ class AdaptiveBlockSparseAttn(nn.Module):
     attention map the reference's docstring describes: ops.sample_offsets -> ops.mask_scores_mass ->
     ops.block_mask_rule, the pooled K/V pass as its own launch). The same seed samples the same tokens
     in both modes; every mask option above works with either. "mass" needs num_keep=32.
+    io_layout: the memory order of what the module returns: "bhld" (default: contiguous [B,H,L,D]) or
+    "blhd": the output lives in [B,L,H,D] memory, the projections' layout, and is returned as its
+    [B,H,L,D] view, so the processors' ``transpose(1, 2).reshape(B, L, H*D)`` is a view instead of a
+    full-tensor copy. Under autograd (both grad_combine forms) the incoming gradient, a transposed view
+    of [B,L,H*D] memory, is read through its strides, and dq, dk and dv come back in that layout too.
+    The kernels store through other strides, nothing else: output values, masks, probe figures and the
+    random stream are bit for bit those of the default.
     """
 
     def __init__(self, variant: str = "cog", *, combine: str = "fused", **overrides):
@@ -237,7 +244,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
                                                "mask_mode", "init_k", "head_budget", "judge_samples",
                                                "judge_key_stride", "judge_top", "judge_clamp", "judge_seed",
                                                "probe", "probe_samples", "probe_seed", "probe_every", "score",
-                                               "grad_combine"}
+                                               "grad_combine", "io_layout"}
         if unknown:
             raise TypeError(f"unknown options {sorted(unknown)}")
         cfg.update(overrides)
@@ -246,6 +253,7 @@ class AdaptiveBlockSparseAttn(nn.Module):
         self.grad_combine = cfg.get("grad_combine", "reference")
         if self.grad_combine not in ("reference", "joint"):
             raise ValueError(f"grad_combine must be 'reference' or 'joint', got {self.grad_combine!r}")
+        self.io_layout = ops.io_layout_code("io_layout", cfg.get("io_layout", "bhld"))
         self.use_rearrange = cfg["use_rearrange"]
         self.max_retain_ratio = cfg["max_retain_ratio"]
         self.min_retain_ratio = cfg["min_retain_ratio"]
@@ -665,11 +673,11 @@ class AdaptiveBlockSparseAttn(nn.Module):
         if joint:
             from .autograd import adaptive_joint_attention
             out = adaptive_joint_attention(q, k, v, mask, rows, self.sample_gap, self._log_gap(q.dtype),
-                                           heavy_rows=self.force_tail, pooled=pooled)
+                                           heavy_rows=self.force_tail, pooled=pooled, io_layout=self.io_layout)
         elif not fused:
             from .autograd import adaptive_split_attention
             out = adaptive_split_attention(q, k, v, mask, rows, self.sample_gap,
-                                           heavy_rows=self.force_tail)
+                                           heavy_rows=self.force_tail, io_layout=self.io_layout)
         else:
             # q rows gathered and out rows scattered inside the attention kernel
             if len(pooled) == 4:   # Gilbert-ordered copies: streamed contiguously
@@ -689,7 +697,8 @@ class AdaptiveBlockSparseAttn(nn.Module):
             out = ops.attention_fwd(q, k_src, v_src, block_mask=mask, q_rows=rows, kv_rows=kv_rows,
                                     kp=kp, vp=vp, kp_log_bias=self._log_gap(q.dtype),
                                     heavy_rows=self.force_tail, order=self.order, q_lengths=rows_kept,
-                                    order_window=self.order_window, persistent=self.persistent)
+                                    order_window=self.order_window, persistent=self.persistent,
+                                    out_layout=self.io_layout)
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()

@@ -26,6 +26,13 @@ FORK_POOLED_BRANCH = True
 _SIDE_STREAMS = {}
 
 
+def _dout(dout: torch.Tensor, io_layout: str) -> torch.Tensor:
+    """The incoming gradient as the backward ops take it: a contiguous copy on the default path, as it
+    comes with io_layout "blhd" (the ops read it through its strides and copy only what misses the
+    16-byte rule)."""
+    return dout if io_layout == "blhd" else dout.contiguous()
+
+
 def _side_stream(dev: torch.device) -> torch.cuda.Stream:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     st = _SIDE_STREAMS.get(idx)
@@ -76,7 +83,7 @@ def block_sparse_attn_func(q_unpad, k_unpad, v_unpad, cu_seqlens_q, cu_seqlens_k
 
 class _AdaptiveSplitFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, mask, rows, gap, heavy_rows):
+    def forward(ctx, q, k, v, mask, rows, gap, heavy_rows, io_layout="bhld"):
         kp, vp, k_r, v_r = ops.pool_kv(k, v, gap, rows, reordered=True)
         # the persistent (work-queue) launch at D=128: Wan's LSE forward 1.024-1.030x, CogVideoX's
         # 0.98x (profiles/r06_persist_unscoped_ab.log); bit-identical either way
@@ -100,10 +107,13 @@ class _AdaptiveSplitFn(torch.autograd.Function):
                     t.record_stream(side)
             out2.record_stream(cur)
             lse2.record_stream(cur)
-        out, alpha = ops.lse_combine(out1, lse1, out2, lse2, gap)
+        # io_layout "blhd": the combine (the call's last pass) stores the output in projection layout
+        # through its strides; the two branch outputs stay contiguous, they never leave this function
+        out, alpha = ops.lse_combine(out1, lse1, out2, lse2, gap, out_layout=io_layout)
         ctx.save_for_backward(q, k_r, v_r, mask, rows, out1, lse1, out2, lse2, alpha, kp, vp)
         ctx.gap = gap
         ctx.heavy_rows = heavy_rows
+        ctx.io_layout = io_layout
         return out
 
     @staticmethod
@@ -111,15 +121,19 @@ class _AdaptiveSplitFn(torch.autograd.Function):
         q, k_r, v_r, mask, rows, out1, lse1, out2, lse2, alpha, kp, vp = ctx.saved_tensors
         # per-branch FA2 backward with dO1 = alpha*dO, dO2 = (1-alpha)*dO; pooled-branch K/V grads
         # through the mean pool and the Gilbert gather, returned in the caller's row order
-        dq, dk, dv = ops.attention_bwd(dout.contiguous(), q, k_r, v_r, out1, lse1, block_mask=mask,
+        dq, dk, dv = ops.attention_bwd(_dout(dout, ctx.io_layout), q, k_r, v_r, out1, lse1, block_mask=mask,
                                        q_rows=rows, kv_rows=rows, kp=kp, vp=vp, out2=out2,
-                                       lse2=lse2, alpha=alpha, gap=ctx.gap, heavy_rows=ctx.heavy_rows)
-        return dq, dk, dv, None, None, None, None
+                                       lse2=lse2, alpha=alpha, gap=ctx.gap, heavy_rows=ctx.heavy_rows,
+                                       grad_layout=ctx.io_layout)
+        return dq, dk, dv, None, None, None, None, None
 
 
-def adaptive_split_attention(q, k, v, mask, rows, gap, heavy_rows=2):
-    """heavy_rows: forced-dense tail rows dispatched first (CogVideoX 2, Wan 0); scheduling only."""
-    return _AdaptiveSplitFn.apply(q, k, v, mask, rows, gap, heavy_rows)
+def adaptive_split_attention(q, k, v, mask, rows, gap, heavy_rows=2, io_layout="bhld"):
+    """heavy_rows: forced-dense tail rows dispatched first (CogVideoX 2, Wan 0); scheduling only.
+    io_layout: "bhld" (default) or "blhd": the output and dq, dk, dv are the [B,H,L,D] views of
+    [B,L,H,D] memory (the projections' layout) and the incoming gradient is read through its strides
+    (a copy only when it misses the kernels' 16-byte rule). The same values either way."""
+    return _AdaptiveSplitFn.apply(q, k, v, mask, rows, gap, heavy_rows, ops.io_layout_code("io_layout", io_layout))
 
 
 class _AdaptiveJointFn(torch.autograd.Function):
@@ -128,13 +142,14 @@ class _AdaptiveJointFn(torch.autograd.Function):
     backward folds the pooled keys' gradients through the mean pool and scatters to the caller's rows."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled):
+    def forward(ctx, q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled, io_layout="bhld"):
         kp, vp, k_r, v_r = pooled if pooled is not None else ops.pool_kv(k, v, gap, rows, reordered=True)
         out, lse = ops.attention_fwd(q, k_r, v_r, block_mask=mask, q_rows=rows, kp=kp, vp=vp,
                                      kp_log_bias=kp_log_bias, need_lse=True, heavy_rows=heavy_rows,
-                                     persistent=q.shape[-1] == 128)
+                                     persistent=q.shape[-1] == 128, out_layout=io_layout)
         ctx.save_for_backward(q, k_r, v_r, kp, vp, out, lse, mask, rows)
         ctx.gap = gap
+        ctx.io_layout = io_layout
         ctx.kp_log_bias = kp_log_bias
         ctx.heavy_rows = heavy_rows
         return out
@@ -142,20 +157,23 @@ class _AdaptiveJointFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         q, k_r, v_r, kp, vp, out, lse, mask, rows = ctx.saved_tensors
-        dq, dk, dv = ops.attention_bwd_joint(dout.contiguous(), q, k_r, v_r, out, lse, block_mask=mask,
+        dq, dk, dv = ops.attention_bwd_joint(_dout(dout, ctx.io_layout), q, k_r, v_r, out, lse, block_mask=mask,
                                              q_rows=rows, kv_rows=rows, kp=kp, vp=vp, gap=ctx.gap,
-                                             kp_log_bias=ctx.kp_log_bias, heavy_rows=ctx.heavy_rows)
-        return dq, dk, dv, None, None, None, None, None, None
+                                             kp_log_bias=ctx.kp_log_bias, heavy_rows=ctx.heavy_rows,
+                                             grad_layout=ctx.io_layout)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
-def adaptive_joint_attention(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows=2, pooled=None):
+def adaptive_joint_attention(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows=2, pooled=None, io_layout="bhld"):
     """The one-softmax form the inference call evaluates (block-masked keys ∪ pooled keys with the
     logit bias ``kp_log_bias``), differentiable in q, k, v with its exact gradient: the mask is a
     constant, the pooled keys are the mean pool of the reordered k/v. ``pooled``: (kp, vp, k_r, v_r)
     already computed from the detached k/v (ops.pool_kv(..., reordered=True), or the predictor's
     pool= outputs), or None to run ops.pool_kv here. One attention launch forward, one
-    ops.attention_bwd_joint call backward; saves q, k_r, v_r, kp, vp, out, lse, mask, rows."""
-    return _AdaptiveJointFn.apply(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled)
+    ops.attention_bwd_joint call backward; saves q, k_r, v_r, kp, vp, out, lse, mask, rows.
+    ``io_layout``: as adaptive_split_attention."""
+    return _AdaptiveJointFn.apply(q, k, v, mask, rows, gap, kp_log_bias, heavy_rows, pooled,
+                                  ops.io_layout_code("io_layout", io_layout))
 
 
 class _QkPrologueFn(torch.autograd.Function):

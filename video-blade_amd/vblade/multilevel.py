@@ -96,34 +96,42 @@ class _SparseAttention(torch.autograd.Function):
     """The multi-level op with the reference kernel's autograd contract (:1580-1588)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, level_mask, sm_scale, ref_tail, rows=None):
+    def forward(ctx, q, k, v, level_mask, sm_scale, ref_tail, rows=None, io_layout="bhld"):
+        ops.io_layout_code("io_layout", io_layout)
         mask_u8 = level_mask.to(torch.uint8).contiguous()
         kpyr, vpyr = ops.kv_pyramid(k, v, rows)
         out, lse = ops.ml_attention_fwd(q, kpyr, vpyr, mask_u8, q_rows=rows, scale=sm_scale,
-                                        ref_tail=ref_tail, want_lse=True)
+                                        ref_tail=ref_tail, want_lse=True, out_layout=io_layout)
         ctx.save_for_backward(q, kpyr, vpyr, mask_u8, out, lse, rows)
         ctx.sm_scale = sm_scale
         ctx.ref_tail = ref_tail
+        ctx.io_layout = io_layout
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, kpyr, vpyr, mask_u8, out, lse, rows = ctx.saved_tensors
-        dq, dk, dv = ops.ml_attention_bwd(dout.contiguous(), q, kpyr, vpyr, mask_u8, out, lse,
-                                          rows=rows, scale=ctx.sm_scale, ref_tail=ctx.ref_tail)
-        return dq, dk, dv, None, None, None, None
+        # io_layout "blhd": dout read through its strides, dq/dk/dv in projection layout
+        blhd = ctx.io_layout == "blhd"
+        dq, dk, dv = ops.ml_attention_bwd(dout if blhd else dout.contiguous(), q, kpyr, vpyr, mask_u8, out, lse,
+                                          rows=rows, scale=ctx.sm_scale, ref_tail=ctx.ref_tail,
+                                          grad_layout=ctx.io_layout)
+        return dq, dk, dv, None, None, None, None, None
 
 
-def sparse_attention_factory(BLOCK_M=128, BLOCK_N=128, POOLING_BLOCK_N=128, ref_tail=True, **kwargs):
+def sparse_attention_factory(BLOCK_M=128, BLOCK_N=128, POOLING_BLOCK_N=128, ref_tail=True, io_layout="bhld",
+                             **kwargs):
     """kernels/block_sparse_attn_kernel_with_backward_9_10.py:1590-1612: returns
     ``fn(q, k, v, level_mask, sm_scale=None) -> out``. Block sizes other than 128 are not
-    supported (the reference's sampler uses 128/128/128)."""
+    supported (the reference's sampler uses 128/128/128). ``io_layout`` "blhd": out and dq, dk, dv in
+    the projections' [B,L,H,D] memory (AdaptiveBlockSparseAttnTrain's option of that name)."""
+    ops.io_layout_code("io_layout", io_layout)
     if (BLOCK_M, BLOCK_N, POOLING_BLOCK_N) != (128, 128, 128):
         raise ValueError("vblade: the multi-level op is built for BLOCK_M = BLOCK_N = POOLING_BLOCK_N = 128")
 
     def fn(q, k, v, block_sparse_dense, sm_scale=None):
         scale = sm_scale if sm_scale is not None else q.shape[-1] ** -0.5
-        return _SparseAttention.apply(q, k, v, block_sparse_dense, scale, ref_tail)
+        return _SparseAttention.apply(q, k, v, block_sparse_dense, scale, ref_tail, None, io_layout)
 
     return fn
 
@@ -137,7 +145,8 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
 
     def __init__(self, *, mask_ratios=None, ref_tail: bool = True, log_every: int = 600,
                  overlap: bool = True, persistent: bool = False, num_keep: int = 32,
-                 probe=None, probe_samples: int = 30, probe_seed: int = 0, probe_every: int = 1, **overrides):
+                 probe=None, probe_samples: int = 30, probe_seed: int = 0, probe_every: int = 1,
+                 io_layout: str = "bhld", **overrides):
         """num_keep: tokens the mask predictor samples per block (16, 32 or 64; default 32).
         overlap: run the KV pyramid pass inside the predictor's launch (True) or as its own
         launch after it. persistent: the attention launch is resident-sized and pulls q-blocks
@@ -147,8 +156,13 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
         (ops.attn_fidelity), as AdaptiveBlockSparseAttn's option of that name does: the same draw from
         ``probe_seed``, the buffer ``probe_rows``, ``last_fidelity_err`` / ``_sig`` / ``_peak`` on the
         device and the ``fidelity`` property. Output, mask and random stream are those of a module
-        without the option."""
+        without the option.
+        io_layout: "bhld" (default) or "blhd": the output (and under autograd dq, dk, dv) in the
+        projections' [B,L,H,D] memory, returned as [B,H,L,D] views, so the caller's
+        transpose(1, 2).reshape(B, L, H*D) is a view; the incoming gradient is read through its strides.
+        The same values, masks and random stream."""
         super().__init__()
+        self.io_layout = ops.io_layout_code("io_layout", io_layout)
         cfg = dict(DEFAULTS)
         unknown = set(overrides) - set(cfg)
         if unknown:
@@ -235,7 +249,7 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
                                                  num_keep=self.num_keep)
                 else:
                     mask = level_mask.to(torch.uint8).contiguous()
-            out = _SparseAttention.apply(q, k, v, mask, q.shape[-1] ** -0.5, self.ref_tail, rows)
+            out = _SparseAttention.apply(q, k, v, mask, q.shape[-1] ** -0.5, self.ref_tail, rows, self.io_layout)
             self._probe(q, k, v, out)
             self.last_mask = mask
             self.sparsity_acc += 1.0 - density(self.mask_ratios)
@@ -265,7 +279,7 @@ class AdaptiveBlockSparseAttnTrain(nn.Module):
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
             out = ops.ml_attention_fwd(q, kpyr, vpyr, mask, q_rows=rows, ref_tail=self.ref_tail,
-                                       heavy_rows=2, persistent=self.persistent)
+                                       heavy_rows=2, persistent=self.persistent, out_layout=self.io_layout)
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()

@@ -67,6 +67,24 @@ def _aligned_bhld(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+IO_LAYOUTS = ("bhld", "blhd")   # memory order of a [B,H,L,D] tensor the library allocates
+
+
+def io_layout_code(name: str, layout: str) -> str:
+    if layout not in IO_LAYOUTS:
+        raise ValueError(f"{name} must be one of {list(IO_LAYOUTS)}, got {layout!r}")
+    return layout
+
+
+def _empty_bhld(B: int, H: int, L: int, D: int, dev, dtype, layout: str = "bhld") -> torch.Tensor:
+    """An uninitialised [B,H,L,D] tensor: contiguous ("bhld"), or the [B,H,L,D] view of [B,L,H,D]
+    memory ("blhd", the projections' [B,L,H*D] layout: transpose(1, 2).reshape(B, L, H*D) of it is a
+    view). The kernels address either through its strides."""
+    if layout == "blhd":
+        return torch.empty(B, L, H, D, device=dev, dtype=dtype).transpose(1, 2)
+    return torch.empty(B, H, L, D, device=dev, dtype=dtype)
+
+
 _WORK_QUEUES = {}
 
 
@@ -118,7 +136,8 @@ def attention_fwd(q: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.
                   scale: Optional[float] = None, need_lse: bool = False,
                   out: Optional[torch.Tensor] = None, heavy_rows: int = 0, order: bool = False,
                   q_lengths: Optional[torch.Tensor] = None, order_window: int = 0,
-                  q_order_out: Optional[torch.Tensor] = None, persistent: bool = False):
+                  q_order_out: Optional[torch.Tensor] = None, persistent: bool = False,
+                  out_layout: str = "bhld"):
     """vb_attn_fwd: softmax over (block-masked keys of k/v) ∪ (pooled keys kp/vp + bias).
     q,k,v [B,H,L,D]; block_mask [B,H,ceil(Lq/128),ceil(Lk/128)] bool/uint8; rows int32.
     ``order``: dispatch each XCD's q-blocks longest first (scheduling only; ``q_lengths`` [B,H,nbq]
@@ -127,7 +146,12 @@ def attention_fwd(q: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.
     ``q_order_out``: int32 [B*H*ceil(Lq/128)] to receive the dispatch permutation, for tests).
     ``persistent``: a resident-sized launch whose workgroups pull q-blocks from per-XCD queues
     (work_queue(); scheduling only, the same outputs).
+    ``out_layout``: the memory order of the output allocated here: "bhld" (contiguous) or "blhd" (the
+    [B,H,Lq,D] view of [B,Lq,H,D] memory, the projections' layout; the same values, stored through
+    other strides). ``out``: a caller's [B,H,Lq,D] buffer instead, of any layout with unit d-stride,
+    the other strides multiples of 8 elements and a 16-byte aligned base; it is written in place.
     Returns out [B,H,Lq,D] (and lse fp32 [B,H,Lq] when need_lse)."""
+    io_layout_code("out_layout", out_layout)
     dev = _require_gpu(q, k, v, block_mask, q_rows, kv_rows, kp, vp, q_lengths, q_order_out)
     q = _aligned_bhld(q)
     B, H, Lq, D = q.shape
@@ -139,7 +163,7 @@ def attention_fwd(q: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.
     if kp is not None:
         kp, vp = _aligned_bhld(kp), _aligned_bhld(vp)
     if out is None:
-        out = torch.empty(B, H, Lq, D, device=dev, dtype=q.dtype)
+        out = _empty_bhld(B, H, Lq, D, dev, q.dtype, out_layout)
     lse = torch.empty(B, H, Lq, device=dev, dtype=torch.float32) if need_lse else None
     a = AttnArgs()
     a.q = q.data_ptr()
@@ -255,7 +279,7 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
                   kp=None, vp=None, out2=None, lse2=None, alpha=None, gap: int = 0,
                   scale: Optional[float] = None, heavy_rows: int = 0, dk_rows: Optional[int] = None,
                   kernel_select: int = 0, kernels_ran: Optional[list] = None,
-                  workspace_bytes: Optional[list] = None):
+                  workspace_bytes: Optional[list] = None, grad_layout: str = "bhld", grads=None):
     """vb_attn_bwd: gradients (dq, dk, dv) of the block-sparse attention, optionally of the
     adaptive two-branch form (kp/vp/out2/lse2/alpha/gap: alpha detached, pooled grads folded back
     through the mean pool). k/v hold keys in reordered order; dk/dv rows are written at
@@ -263,15 +287,21 @@ def attention_bwd(dout, q, k, v, out, lse, *, block_mask=None, q_rows=None, kv_r
     ``kernel_select``: _lib.VB_BWD_SEL_* bits (0: the default kernels); ``kernels_ran`` (a list)
     receives the _lib.VB_BWD_RAN_* bits of the kernels the call launched; ``workspace_bytes`` (a
     list) the size vb_attn_bwd_workspace_size reported for the call (it holds psplit copies of the
-    pooled-key partials, so tests read the pooled-key split from it)."""
+    pooled-key partials, so tests read the pooled-key split from it).
+    ``dout`` is read through its strides (a transposed view of [B,L,H*D] memory as it comes; copied
+    only when its strides or base miss the 16-byte rule). ``grad_layout``: the memory order of dq, dk
+    and dv, "bhld" (contiguous) or "blhd" (the [B,H,L,D] views of [B,L,H,D] memory). ``grads``: (dq,
+    dk, dv) buffers of the caller instead, as ml_attention_bwd's."""
     return _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2, alpha, gap,
-                          scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, None)
+                          scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, None,
+                          grad_layout, grads)
 
 
 def attention_bwd_joint(dout, q, k, v, out, lse, *, block_mask, q_rows, kv_rows, kp, vp, gap: int,
                         kp_log_bias: float, scale: Optional[float] = None, heavy_rows: int = 0,
                         dk_rows: Optional[int] = None, kernel_select: int = 0,
-                        kernels_ran: Optional[list] = None, workspace_bytes: Optional[list] = None):
+                        kernels_ran: Optional[list] = None, workspace_bytes: Optional[list] = None,
+                        grad_layout: str = "bhld", grads=None):
     """vb_attn_bwd_joint: the exact gradients (dq, dk, dv) of the one softmax attention_fwd evaluates
     with kp/vp/kp_log_bias: ``out`` and ``lse`` are that call's (need_lse=True, the same kp_log_bias),
     the block mask is a constant, and kp/vp are the mean pool of the reordered k/v over ``gap`` keys, so
@@ -281,21 +311,31 @@ def attention_bwd_joint(dout, q, k, v, out, lse, *, block_mask, q_rows, kv_rows,
         raise ValueError("attention_bwd_joint: the joint softmax needs the pooled keys kp and vp")
     return _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, None, None, None, gap,
                           scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes,
-                          float(kp_log_bias))
+                          float(kp_log_bias), grad_layout, grads)
 
 
 def _attention_bwd(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2, alpha, gap,
-                   scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, joint_bias):
+                   scale, heavy_rows, dk_rows, kernel_select, kernels_ran, workspace_bytes, joint_bias,
+                   grad_layout="bhld", grads=None):
     """attention_bwd (``joint_bias`` None) and attention_bwd_joint (the pooled keys' logit bias)."""
+    io_layout_code("grad_layout", grad_layout)
     dev = _require_gpu(dout, q, k, v, out, lse, block_mask, q_rows, kv_rows, kp, vp, out2, lse2,
                        alpha)
     q, k, v, out, dout = (_aligned_bhld(t) for t in (q, k, v, out, dout))
     B, H, Lq, D = q.shape
     Lk = k.shape[2]
     nrows = Lk if dk_rows is None else int(dk_rows)
-    dq = torch.empty(B, H, Lq, D, device=dev, dtype=q.dtype)
-    dk = torch.empty(B, H, nrows, D, device=dev, dtype=q.dtype)
-    dv = torch.empty(B, H, nrows, D, device=dev, dtype=q.dtype)
+    if grads is None:
+        dq = _empty_bhld(B, H, Lq, D, dev, q.dtype, grad_layout)
+        dk = _empty_bhld(B, H, nrows, D, dev, q.dtype, grad_layout)
+        dv = _empty_bhld(B, H, nrows, D, dev, q.dtype, grad_layout)
+    else:
+        dq, dk, dv = grads
+        for name, t, n in (("dq", dq, Lq), ("dk", dk, nrows), ("dv", dv, nrows)):
+            _check_dev(f"attention_bwd: grads {name}", t, dev)
+            if tuple(t.shape) != (B, H, n, D) or t.dtype != q.dtype:
+                raise ValueError(f"attention_bwd: grads {name} must be [{B},{H},{n},{D}] {q.dtype}, got "
+                                 f"{tuple(t.shape)} {t.dtype}")
     a = BwdArgs()
     a.q, a.q_stride = q.data_ptr(), _s3(q)
     a.k, a.v, a.k_stride, a.v_stride = k.data_ptr(), v.data_ptr(), _s3(k), _s3(v)
@@ -1074,14 +1114,38 @@ def pool_kv(k, v, gap: int, rows=None, reordered: bool = False, stream=None, out
     return kp, vp
 
 
-def lse_combine(out1, lse1, out2, lse2, gap: float):
-    """vb_lse_combine (reference-faithful eager rounding). Returns (out, alpha fp32 [B,H,L])."""
-    dev = _require_gpu(out1, lse1, out2, lse2)
-    out1, out2 = out1.contiguous(), out2.contiguous()
-    lse1, lse2 = lse1.float().contiguous(), lse2.float().contiguous()
+def lse_combine(out1, lse1, out2, lse2, gap: float, *, out_layout: str = "bhld", out=None):
+    """vb_lse_combine (reference-faithful eager rounding). Returns (out, alpha fp32 [B,H,L]).
+    ``out_layout``: the memory order of the output allocated here ("bhld" contiguous, "blhd" the
+    [B,H,L,D] view of [B,L,H,D] memory); ``out``: a caller's [B,H,L,D] buffer instead (unit d-stride,
+    the other strides multiples of 8 elements, 16-byte aligned base, no overlap with the inputs). When
+    out1, out2 or the output is not contiguous and D is 64 or 128 the call goes to
+    vb_lse_combine_strided, which reads and writes through the strides: the same bits, no copies."""
+    io_layout_code("out_layout", out_layout)
+    dev = _require_gpu(out1, lse1, out2, lse2, out)
     B, H, L, D = out1.shape
-    out = torch.empty_like(out1)
+    if out is not None and (tuple(out.shape) != (B, H, L, D) or out.dtype != out1.dtype):
+        raise ValueError(f"lse_combine: out must be [{B},{H},{L},{D}] {out1.dtype}, got {tuple(out.shape)} {out.dtype}")
+    if out is not None and out.data_ptr() in (out1.data_ptr(), out2.data_ptr()):
+        raise ValueError("lse_combine: out may not overlap the inputs")
+    lse1, lse2 = lse1.float().contiguous(), lse2.float().contiguous()
     alpha = torch.empty(B, H, L, device=dev, dtype=torch.float32)
+    if D in (64, 128):
+        out1, out2 = _aligned_bhld(out1), _aligned_bhld(out2)
+        if out is None:
+            out = _empty_bhld(B, H, L, D, dev, out1.dtype, out_layout)
+        if not (out1.is_contiguous() and out2.is_contiguous() and out.is_contiguous()):
+            cast = lambda t: ctypes.cast(_s3(t), ctypes.c_void_p)
+            check(_lib.load().vb_lse_combine_strided(
+                out1.data_ptr(), cast(out1), lse1.data_ptr(), out2.data_ptr(), cast(out2), lse2.data_ptr(),
+                B, H, L, D, float(gap), _dtype_code(out1), out.data_ptr(), cast(out), alpha.data_ptr(),
+                _stream(dev)), "vb_lse_combine_strided")
+            return out, alpha
+    elif out_layout != "bhld" or (out is not None and not out.is_contiguous()):
+        raise ValueError(f"lse_combine: a strided output needs D = 64 or 128, got {D}")
+    out1, out2 = out1.contiguous(), out2.contiguous()
+    if out is None:
+        out = torch.empty_like(out1)
     check(_lib.load().vb_lse_combine(out1.data_ptr(), lse1.data_ptr(), out2.data_ptr(),
                                      lse2.data_ptr(), B, H, L, D, float(gap), _dtype_code(out1),
                                      out.data_ptr(), alpha.data_ptr(), _stream(dev)),
@@ -1408,9 +1472,12 @@ def level_mask(po, ratios=None):
 
 
 def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, ref_tail=True,
-                     want_lse=False, heavy_rows=2, out=None, persistent: bool = False):
+                     want_lse=False, heavy_rows=2, out=None, persistent: bool = False,
+                     out_layout: str = "bhld"):
     """vb_ml_attn_fwd: multi-level attention of q [B,H,L,D] over the KV pyramids. Returns out
-    (rows through q_rows) and, if want_lse, the fp32 natural-log LSE [B,H,L] (reordered rows)."""
+    (rows through q_rows) and, if want_lse, the fp32 natural-log LSE [B,H,L] (reordered rows).
+    ``out_layout`` / ``out``: as attention_fwd."""
+    io_layout_code("out_layout", out_layout)
     dev = _require_gpu(q, kpyr, vpyr, level_mask_u8, q_rows)
     q = _aligned_bhld(q)
     B, H, L, D = q.shape
@@ -1425,7 +1492,10 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
     if m.stride(-1) != 1:
         m = m.contiguous()
     if out is None:
-        out = torch.empty_like(q) if q.is_contiguous() else torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+        if out_layout == "blhd":
+            out = _empty_bhld(B, H, L, D, dev, q.dtype, out_layout)
+        else:
+            out = torch.empty_like(q) if q.is_contiguous() else torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
     lse = torch.empty(B, H, L, device=dev, dtype=torch.float32) if want_lse else None
     a = MlAttnArgs()
     a.q, a.q_stride, a.q_rows = q.data_ptr(), _s3(q), _ptr(q_rows)
@@ -1446,7 +1516,7 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
 
 def ml_attention_bwd(dout, q, kpyr, vpyr, level_mask_u8, out, lse, *, rows=None, scale=None,
                      ref_tail=True, heavy_rows=2, kernel_select: int = 0, kernels_ran: Optional[list] = None,
-                     grads=None, workspace_bytes: Optional[list] = None):
+                     grads=None, workspace_bytes: Optional[list] = None, grad_layout: str = "bhld"):
     """vb_ml_attn_bwd: gradients of the multi-level attention. q/out/dout [B,H,L,D] (rows through
     ``rows``), pyramids and mask as the forward; lse as ml_attention_fwd(want_lse=True) wrote it.
     Returns (dq, dk, dv) [B,H,L,D] in q's dtype (dk/dv at the caller's rows). ``kernel_select`` /
@@ -1454,16 +1524,17 @@ def ml_attention_bwd(dout, q, kpyr, vpyr, level_mask_u8, out, lse, *, rows=None,
     buffers of the caller, [B,H,L,D] in q's dtype on q's device, any strides the kernels accept
     (unit d-stride, the others multiples of 8 elements, 16-byte aligned); they are fully
     overwritten and returned. ``workspace_bytes`` (a list) receives the size
-    vb_ml_attn_bwd_workspace_size reported for the call."""
+    vb_ml_attn_bwd_workspace_size reported for the call. ``dout`` is read through its strides (copied
+    only when it misses the 16-byte rule); ``grad_layout``: the memory order of the dq, dk, dv
+    allocated here (without ``grads``), "bhld" or "blhd" as attention_bwd."""
+    io_layout_code("grad_layout", grad_layout)
     dev = _require_gpu(dout, q, kpyr, vpyr, level_mask_u8, out, lse, rows)
     q, out, dout = _aligned_bhld(q), _aligned_bhld(out), _aligned_bhld(dout)
     B, H, L, D = q.shape
     m = level_mask_u8 if level_mask_u8.stride(-1) == 1 else level_mask_u8.contiguous()
     lse = lse.float().contiguous()
     if grads is None:
-        dq = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
-        dk = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
-        dv = torch.empty(B, H, L, D, device=dev, dtype=q.dtype)
+        dq, dk, dv = (_empty_bhld(B, H, L, D, dev, q.dtype, grad_layout) for _ in range(3))
     else:
         dq, dk, dv = grads
         for name, t in (("dq", dq), ("dk", dk), ("dv", dv)):

@@ -53,6 +53,11 @@ def _prologue_inputs_ok(query, key, value, heads, head_dim, *params, backward: b
     return True
 
 
+def _shares_storage(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Whether a is a view of b's memory (no copy was made between them)."""
+    return a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
 def _norm_params(norm):
     return [] if norm is None else [getattr(norm, "weight", None), getattr(norm, "bias", None)]
 
@@ -91,13 +96,20 @@ class CogVideoXBlockSparseAttnProcessor:
     ``fused_qk``: norm_q/norm_k and RoPE in one library pass where the call allows it (see
     ``_fused_qk``); ``last_path`` tells which chain the last call took, "fused" or "eager".
     ``fused_qk_backward`` (with ``fused_qk``): a call that records autograd takes the fused pass too,
-    through autograd.qk_prologue, instead of keeping the eager chain."""
+    through autograd.qk_prologue, instead of keeping the eager chain.
+    ``projection_layout``: the setter's flag (the shared module then returns its output in the
+    projections' [B,L,H*D] memory, io_layout="blhd"), kept here for inspection; ``last_out_is_view``
+    tells whether the tensor the last call gave to ``to_out[0]`` shared storage with what
+    ``inner_attention`` returned (True: the reshape below was a view) or was a copy of it."""
 
-    def __init__(self, idx: int = 0, fused_qk: bool = False, fused_qk_backward: bool = False):
+    def __init__(self, idx: int = 0, fused_qk: bool = False, fused_qk_backward: bool = False,
+                 projection_layout: bool = False):
         self.idx = idx
         self.fused_qk = fused_qk
         self.fused_qk_backward = fused_qk_backward
+        self.projection_layout = projection_layout
         self.last_path = None
+        self.last_out_is_view = None
 
     def _fused_qk(self, attn, query, key, value, head_dim, text_seq_length, image_rotary_emb):
         """(q, k) [B,H,L,D] from the [B,L,H*D] projections through ops.qk_prologue, or None when this
@@ -159,7 +171,9 @@ class CogVideoXBlockSparseAttnProcessor:
                     key[:, :, text_seq_length:] = _apply_rotary_emb_real(key[:, :, text_seq_length:], image_rotary_emb)
             value = value.contiguous()
         hidden_states = attn.inner_attention(query, key, value)
+        attn_out = hidden_states
         hidden_states = hidden_states.transpose(1, 2).reshape(batch_size, -1, attn.heads * head_dim)
+        self.last_out_is_view = _shares_storage(hidden_states, attn_out)
         hidden_states = attn.to_out[0](hidden_states)
         hidden_states = attn.to_out[1](hidden_states)
         encoder_hidden_states, hidden_states = hidden_states.split(
@@ -167,20 +181,35 @@ class CogVideoXBlockSparseAttnProcessor:
         return hidden_states, encoder_hidden_states
 
 
+def _projection_layout(attn_kwargs) -> bool:
+    """Pop the setters' ``projection_layout`` flag; True selects the module's io_layout="blhd"."""
+    flag = bool(attn_kwargs.pop("projection_layout", False))
+    if flag:
+        if attn_kwargs.get("io_layout", "blhd") != "blhd":
+            raise ValueError("projection_layout=True is io_layout='blhd'; got io_layout="
+                             f"{attn_kwargs['io_layout']!r} as well")
+        attn_kwargs["io_layout"] = "blhd"
+    return flag
+
+
 def set_block_sparse_attn_cogvideox(model, verbose: bool = False, **attn_kwargs):
     """modify_cogvideo.py:79-91: ONE shared inner-attention module on every transformer block's
     attn1, processor swapped, the original kept as ``origin_processor``. Returns the module.
     ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE;
-    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training)."""
+    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training).
+    ``projection_layout=True`` (default False) sets the shared module's io_layout="blhd": its output
+    (and under autograd dq, dk, dv) live in the projections' [B,L,H*D] memory, so the processors'
+    reshape before ``to_out[0]`` is a view, not a copy (measured: DESIGN.md §3.8)."""
     fused_qk = bool(attn_kwargs.pop("fused_qk", False))
     fused_qk_backward = bool(attn_kwargs.pop("fused_qk_backward", False))
+    projection_layout = _projection_layout(attn_kwargs)
     inner_attn = AdaptiveBlockSparseAttn("cog", **attn_kwargs)
     for idx, block in enumerate(model.transformer_blocks):
         block.attn1.verbose = verbose
         block.attn1.inner_attention = inner_attn
         origin = block.attn1.get_processor() if hasattr(block.attn1, "get_processor") else None
         block.attn1.set_processor(CogVideoXBlockSparseAttnProcessor(
-            idx, fused_qk=fused_qk, fused_qk_backward=fused_qk_backward))
+            idx, fused_qk=fused_qk, fused_qk_backward=fused_qk_backward, projection_layout=projection_layout))
         if not hasattr(block.attn1, "origin_processor"):
             block.attn1.origin_processor = origin
     return inner_attn
@@ -189,12 +218,15 @@ def set_block_sparse_attn_cogvideox(model, verbose: bool = False, **attn_kwargs)
 class WanBlockSparseAttnProcessor:
     """WanAttnProcessor2_0 (modify_wan.py:75-148): video self-attention (attn1) with the
     complex-valued RoPE in float64; the I2V image branch also goes through inner_attention.
-    ``fused_qk`` / ``fused_qk_backward`` / ``last_path``: as CogVideoXBlockSparseAttnProcessor."""
+    ``fused_qk`` / ``fused_qk_backward`` / ``last_path`` / ``projection_layout`` / ``last_out_is_view``: as
+    CogVideoXBlockSparseAttnProcessor."""
 
-    def __init__(self, fused_qk: bool = False, fused_qk_backward: bool = False):
+    def __init__(self, fused_qk: bool = False, fused_qk_backward: bool = False, projection_layout: bool = False):
         self.fused_qk = fused_qk
         self.fused_qk_backward = fused_qk_backward
+        self.projection_layout = projection_layout
         self.last_path = None
+        self.last_out_is_view = None
 
     def _fused_qk(self, attn, query, key, value, rotary_emb):
         """(q, k) [B,H,L,D] through ops.qk_prologue, or None when this call keeps the eager chain: the
@@ -265,7 +297,9 @@ class WanBlockSparseAttnProcessor:
             hidden_states_img = attn.inner_attention(query, key_img, value_img)
             hidden_states_img = hidden_states_img.transpose(1, 2).flatten(2, 3).type_as(query)
         hidden_states = attn.inner_attention(query, key, value)
+        attn_out = hidden_states
         hidden_states = hidden_states.transpose(1, 2).flatten(2, 3).type_as(query)
+        self.last_out_is_view = _shares_storage(hidden_states, attn_out)
         if hidden_states_img is not None:
             hidden_states = hidden_states + hidden_states_img
         hidden_states = attn.to_out[0](hidden_states)
@@ -277,16 +311,19 @@ def set_adaptive_block_sparse_attn_wanx(model, verbose: bool = False, **attn_kwa
     """modify_wan.py:150-168: patch attn1 (self-attention) of every block; attn2 (cross-attention
     to the T5 tokens) keeps stock SDPA. Returns the shared module.
     ``fused_qk=True`` (default False) gives every processor the one-pass q/k norm + RoPE;
-    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training)."""
+    ``fused_qk_backward=True`` (default False) keeps it under autograd as well (training).
+    ``projection_layout=True`` (default False): as set_block_sparse_attn_cogvideox."""
     fused_qk = bool(attn_kwargs.pop("fused_qk", False))
     fused_qk_backward = bool(attn_kwargs.pop("fused_qk_backward", False))
+    projection_layout = _projection_layout(attn_kwargs)
     inner_attn = AdaptiveBlockSparseAttn("wan", **attn_kwargs)
     for block in model.blocks:
         block.attn1.verbose = verbose
         block.attn1.inner_attention = inner_attn
         origin = block.attn1.get_processor() if hasattr(block.attn1, "get_processor") else None
         block.attn1.set_processor(WanBlockSparseAttnProcessor(fused_qk=fused_qk,
-                                                               fused_qk_backward=fused_qk_backward))
+                                                               fused_qk_backward=fused_qk_backward,
+                                                               projection_layout=projection_layout))
         if not hasattr(block.attn1, "origin_processor"):
             block.attn1.origin_processor = origin
     return inner_attn

@@ -62,12 +62,16 @@ class LoRALinear(nn.Module):
 
 class StandInAttentionBlock(nn.Module):
     """One transformer block's attention with CogVideoX-5B's geometry: the LoRA targets of the
-    reference (to_q, to_k, to_v, to_out.0) around ``inner_attention(q, k, v)`` on [B,H,L,D]."""
+    reference (to_q, to_k, to_v, to_out.0) around ``inner_attention(q, k, v)`` on [B,H,L,D].
+    ``projection_layout`` (for an ``inner_attention`` built with io_layout="blhd"): v is handed over
+    as the [B,H,L,D] view of its projection, not copied (the kernels read it through its strides, as
+    they read q and k), and the output reshape before ``to_out`` is then a view as well."""
 
     def __init__(self, hidden: int, heads: int, rank: int, alpha: float, inner_attention: nn.Module, *,
-                 dtype=torch.bfloat16, device=None, generator=None):
+                 dtype=torch.bfloat16, device=None, generator=None, projection_layout: bool = False):
         super().__init__()
         self.heads = heads
+        self.projection_layout = bool(projection_layout)
         self.norm = nn.LayerNorm(hidden, elementwise_affine=False)
         kw = dict(dtype=dtype, device=device, generator=generator)
         self.to_q = LoRALinear(hidden, hidden, rank, alpha, **kw)
@@ -85,7 +89,7 @@ class StandInAttentionBlock(nn.Module):
             return t.view(B, L, self.heads, D).transpose(1, 2)
 
         q, k, v = heads(self.to_q(h)), heads(self.to_k(h)), heads(self.to_v(h))
-        o = self.inner_attention(q, k, v.contiguous())
+        o = self.inner_attention(q, k, v if self.projection_layout else v.contiguous())
         o = o.transpose(1, 2).reshape(B, L, C)
         return x + self.to_out[0](o)
 
@@ -93,16 +97,17 @@ class StandInAttentionBlock(nn.Module):
 class StandInTransformer(nn.Module):
     """``num_layers`` stand-in blocks sharing one ``inner_attention`` module (as
     set_block_sparse_attn_cogvideox installs one instance on every block), with optional
-    per-block gradient checkpointing (the reference's enable_gradient_checkpointing)."""
+    per-block gradient checkpointing (the reference's enable_gradient_checkpointing).
+    ``projection_layout``: every block's flag of that name."""
 
     def __init__(self, num_layers: int, hidden: int, heads: int, rank: int, alpha: float,
                  inner_attention: nn.Module, *, gradient_checkpointing: bool = True,
-                 dtype=torch.bfloat16, device=None, seed: int = 0):
+                 dtype=torch.bfloat16, device=None, seed: int = 0, projection_layout: bool = False):
         super().__init__()
         g = torch.Generator().manual_seed(seed)
         self.transformer_blocks = nn.ModuleList(
             [StandInAttentionBlock(hidden, heads, rank, alpha, inner_attention, dtype=dtype, device=device,
-                                   generator=g) for _ in range(num_layers)])
+                                   generator=g, projection_layout=projection_layout) for _ in range(num_layers)])
         self.gradient_checkpointing = gradient_checkpointing
 
     def forward(self, x, cond: Optional[torch.Tensor] = None):
