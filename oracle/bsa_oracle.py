@@ -311,11 +311,19 @@ def attention_fwd_emulated(q, k, v, block_mask, *, kp=None, vp=None, kp_log_bias
     Rows that see no key: zero output, -inf LSE. Returns fp32 (out, lse)."""
     D = q.shape[-1]
     scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(D)
-    c = np.float32(scale) * LOG2E_F32
     K, V, vis, b = union_keys(q, k, v, block_mask, kp, vp, 0.0, use_main, block)
     bias2 = b.float()   # exp2 domain
     if kp is not None:
         bias2[-kp.shape[2]:] = float(np.float32(kp_log_bias) * LOG2E_F32)
+    return fwd_emulated_over_visible(q, K, V, vis, bias2, scale, store_dtype, prescale_q, m_lag)
+
+
+def fwd_emulated_over_visible(q, K, V, vis, bias2, scale, store_dtype, prescale_q=False, m_lag=None):
+    """The roundings of attention_fwd_emulated over any union of keys: K, V [B,H,n,D] in the storage
+    dtype, ``vis`` bool [B,H,Lq,n], ``bias2`` fp32 [n] the per-key logit bias in the EXP2 domain (what
+    the kernel adds: fp32(kp_log_bias) * fp32(log2 e) for pooled keys, exactly 0, 1, 2, 3 for the
+    multi-level forward's levels). Returns fp32 (out, lse)."""
+    c = np.float32(scale) * LOG2E_F32
     ninf = float("-inf")
     if prescale_q:
         qs = rnd(q.float() * float(c), store_dtype)

@@ -200,6 +200,75 @@ def multilevel_attention(q, k, v, mask, sm_scale=None, ref_tail=True):
     return dict(out=out, l=l_out, m=m_out, lse=m_out + torch.log(l_out))
 
 
+def ml_union_keys(q, k, v, mask, ref_tail=True, q_pos=None):
+    """The multi-level forward as ONE softmax over a union of keys, in bsa_oracle.union_keys' form:
+    the four pyramid levels of k / v [B,H,L,D] (kv_pyramid on the storage-dtype inputs) concatenated
+    to 15*Lpad/8 rows, level-1 rows at or past L zeroed (as vb_kv_pyramid stores them). Key r of
+    level p and key block j is visible to a query row of q-block i iff mask[b,h,i,j] == p (values
+    other than 1, 2, 4, 8 keep nothing). With ``ref_tail`` the zero level-1 keys at or past L stay
+    visible (score 0, value 0: the reference kernel's masked loads); without it they are hidden.
+    ``q_pos`` (int64 [n]): the logical positions of q's rows when q holds a selection of the L rows
+    (default: all of them, in order).
+    Returns (K, V [B,H,R,D] storage dtype, visible bool [B,H,Lq,R], bias fp64 [R] = ln p,
+    key_level int64 [R], key_block int64 [R])."""
+    B, H, _, D = q.shape
+    L = k.shape[2]
+    nb = (L + BLOCK - 1) // BLOCK
+    Lpad = nb * BLOCK
+    K = torch.cat(kv_pyramid(k), dim=2)
+    V = torch.cat(kv_pyramid(v), dim=2)
+    K[:, :, L:Lpad] = 0
+    V[:, :, L:Lpad] = 0
+    key_level = torch.cat([torch.full((Lpad // p,), p, dtype=torch.int64) for p in LEVELS])
+    key_block = torch.cat([torch.arange(Lpad // p) // (BLOCK // p) for p in LEVELS])
+    pos = torch.arange(L) if q_pos is None else q_pos
+    assert pos.numel() == q.shape[2]
+    m = mask.to(torch.int64).expand(B, H, nb, nb)
+    vis = (m[:, :, :, key_block] == key_level)[:, :, pos // BLOCK]
+    if not ref_tail:
+        vis[..., L:Lpad] = False
+    return K, V, vis, key_level.double().log(), key_level, key_block
+
+
+def multilevel_attention_fp64(q, k, v, mask, sm_scale=None, ref_tail=True, q_pos=None):
+    """fp64 reference of vb_ml_attn_fwd: bsa_oracle.softmax_over_visible over ml_union_keys, each
+    key with the logit bias ln p of its level; no intermediate rounding beyond the pyramid's own
+    (each level is a storage-dtype tensor). Returns fp64 (out [B,H,Lq,D], lse [B,H,Lq]); a row whose
+    mask row keeps nothing gives a zero output and a -inf LSE."""
+    import bsa_oracle as O   # oracle dir is on sys.path
+    scale = sm_scale if sm_scale is not None else q.shape[-1] ** -0.5
+    K, V, vis, bias, _, _ = ml_union_keys(q, k, v, mask, ref_tail, q_pos)
+    return O.softmax_over_visible(q, K, V, vis, bias, scale)
+
+
+def multilevel_attention_fwd_emulated(q, k, v, mask, *, sm_scale=None, ref_tail=True, store_dtype,
+                                      prescale_q=False, m_lag=None, q_pos=None):
+    """vb_ml_attn_fwd (the kML arm of csrc/vb_attn_fwd.hip) in fp32 with its roundings: the same
+    core as bsa_oracle.attention_fwd_emulated (fma into the exp2 domain or the pre-scaled Q, P rounded
+    for P.V, l from the unrounded P, the output rounding, (m + log2 l) * ln 2) over ml_union_keys.
+    The exp2-domain bias of a level-p key is exactly log2 p = 0, 1, 2 or 3 (the kernel's bias_bits).
+    Returns fp32 (out, lse)."""
+    import bsa_oracle as O
+    scale = sm_scale if sm_scale is not None else q.shape[-1] ** -0.5
+    K, V, vis, _, key_level, _ = ml_union_keys(q, k, v, mask, ref_tail, q_pos)
+    bias2 = key_level.float().log2()
+    assert bool((bias2 == bias2.round()).all())
+    return O.fwd_emulated_over_visible(q, K, V, vis, bias2, scale, store_dtype, prescale_q, m_lag)
+
+
+def ml_tiles_fed(mask, L, ref_tail):
+    """int64 [B,H,nb]: the 64-row tiles the kernel feeds a q-block: two per level-1 block (minus the
+    empty second half of a kept last block when (nb-1)*128 + 64 >= L, unless ``ref_tail`` keeps the
+    zero-padded keys), one per level-2 block, one per two level-4 and per four level-8 blocks."""
+    nb = (L + BLOCK - 1) // BLOCK
+    m = mask.to(torch.int64)
+    n1, n2, n4, n8 = ((m == p).sum(-1) for p in LEVELS)
+    t = 2 * n1 + n2 + (n4 + 1) // 2 + (n8 + 3) // 4
+    if not ref_tail and (nb - 1) * BLOCK + BLOCK // 2 >= L:
+        t = t - (m[..., -1] == 1).long()
+    return t
+
+
 def multilevel_attention_bwd(q, k, v, mask, out, l, m, dout, sm_scale=None, store_dtype=None):
     """_backward (KML:1375-1576) with the per-level kernels (:696-1237), fp32 arithmetic.
     ``out`` is the forward output as stored (storage dtype values); dO/l is rounded to

@@ -268,15 +268,21 @@ def rows_that_can_lag(q, k, v, mask, kp, vp, bias, scale, use_main, form, dtype)
         training form then raises m to the tile's exact maximum (kRescaleSlack), the inference
         form's half-tile sum exceeds kLazyBound and it does the same; P is exactly 1 either way."""
     K, V, vis, b = O.union_keys(q, k, v, mask, kp, vp, bias, use_main)
+    Lkp = 0 if kp is None else kp.shape[2]
+    n_main = vis[..., :vis.shape[-1] - Lkp].sum(-1)
+    tiles = (n_main > 64) | ((n_main > 0) & (Lkp > 0)) | (Lkp > 64)
+    return lagging_rows_over_visible(q, K, vis, b, scale, tiles, form, dtype)
+
+
+def lagging_rows_over_visible(q, K, vis, b, scale, tiles, form, dtype):
+    """rows_that_can_lag over any union of keys (K [B,H,n,D], ``vis`` bool [B,H,Lq,n], ``b`` the
+    per-key bias in natural-log units); ``tiles`` bool [B,H,Lq]: the row is fed more than one tile."""
     s = (torch.matmul(q.double(), K.double().transpose(-1, -2)) * scale + b).masked_fill(~vis, float("-inf"))
     w = torch.softmax(s, -1)
     owned = torch.where(torch.isnan(w), torch.zeros_like(w), w).amax(-1) > OWNED
     if s.shape[-1] < 2:
         return torch.zeros_like(owned)
     top = s.topk(2, -1).values * math.log2(math.e)
-    Lkp = 0 if kp is None else kp.shape[2]
-    n_main = vis[..., :vis.shape[-1] - Lkp].sum(-1)
-    tiles = (n_main > 64) | ((n_main > 0) & (Lkp > 0)) | (Lkp > 64)
     return owned & tiles & (top[..., 0] - top[..., 1] <= SLACK[form][dtype])
 
 

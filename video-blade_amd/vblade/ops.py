@@ -1475,7 +1475,8 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
                      want_lse=False, heavy_rows=2, out=None, persistent: bool = False,
                      out_layout: str = "bhld"):
     """vb_ml_attn_fwd: multi-level attention of q [B,H,L,D] over the KV pyramids. Returns out
-    (rows through q_rows) and, if want_lse, the fp32 natural-log LSE [B,H,L] (reordered rows).
+    (rows through q_rows) and, if want_lse, the fp32 natural-log LSE [B,H,L] (at the caller's rows
+    q_rows[g], like out: include/vblade.h).
     ``out_layout`` / ``out``: as attention_fwd."""
     io_layout_code("out_layout", out_layout)
     dev = _require_gpu(q, kpyr, vpyr, level_mask_u8, q_rows)
