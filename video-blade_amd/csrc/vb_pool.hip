@@ -39,8 +39,12 @@ __device__ __forceinline__ void lse_combine_weights(float lse1, float lse2, floa
   b = round_to<T>(1.0f - a);
 }
 
+// No contraction here: with fp16 the compiler narrows the three rounded fp32 operations to half
+// arithmetic (the same values) and, contracting, fused v1 * a into the addition (v_pk_fma_f16), which
+// drops the rounding of that product the reference makes (tests/test_gpu_lse_combine.py, check (c)).
 template <class T>
 __device__ __forceinline__ u32x4 lse_combine_chunk(const u32x4& x1, const u32x4& x2, float a, float b) {
+#pragma clang fp contract(off)
   u32x4 y;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {

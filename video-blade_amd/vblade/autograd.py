@@ -86,7 +86,8 @@ class _AdaptiveSplitFn(torch.autograd.Function):
     def forward(ctx, q, k, v, mask, rows, gap, heavy_rows, io_layout="bhld"):
         kp, vp, k_r, v_r = ops.pool_kv(k, v, gap, rows, reordered=True)
         # the persistent (work-queue) launch at D=128: Wan's LSE forward 1.024-1.030x, CogVideoX's
-        # 0.98x (profiles/r06_persist_unscoped_ab.log); bit-identical either way
+        # 0.98x (profiles/r06_persist_unscoped_ab.log); bit-identical either way. Captured into a graph
+        # on a stream that has no queue yet, the launch is per q-block (ops.work_queue makes none there)
         fork = FORK_POOLED_BRANCH and q.is_cuda and q.shape[-1] == 128
         if fork:
             cur = torch.cuda.current_stream(q.device)

@@ -88,17 +88,33 @@ def _empty_bhld(B: int, H: int, L: int, D: int, dev, dtype, layout: str = "bhld"
 _WORK_QUEUES = {}
 
 
-def work_queue(dev) -> torch.Tensor:
+def work_queue(dev) -> Optional[torch.Tensor]:
     """The persistent forward's work queue (include/vblade.h VB_WORK_QUEUE_INTS) for ``dev``'s current
     stream: int32, zero when allocated, and left zero by every launch that uses it. One per (device,
-    stream), since two launches that may overlap must not share one."""
+    stream), since two launches that may overlap must not share one.
+
+    No queue is ever created while the stream is being captured into a graph: the zero-fill would
+    become a graph node that has not run when another graph captured on the same stream finds the
+    cached queue and is replayed first, and the memory would belong to the graph's private pool. With
+    no queue for (device, stream) yet and a capture under way this returns None, allocates nothing
+    and caches nothing; the callers then launch the one-workgroup-per-q-block form. A queue created
+    eagerly beforehand (the warm-up calls torch asks for before a capture) is returned as always."""
     dev = torch.device(dev)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     key = (idx, _stream(dev))
     wq = _WORK_QUEUES.get(key)
     if wq is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None
         wq = _WORK_QUEUES[key] = torch.zeros(_lib.VB_WORK_QUEUE_INTS, device=dev, dtype=torch.int32)
     return wq
+
+
+def _work_queue_ptr(dev, persistent: bool):
+    """vb_attn_args.work_queue of a launch: the stream's queue when ``persistent`` is asked for and a
+    queue may be used (work_queue), else None, the one-workgroup-per-q-block form (the same bits)."""
+    wq = work_queue(dev) if persistent else None
+    return None if wq is None else wq.data_ptr()
 
 
 def _check_dev(name: str, t: torch.Tensor, dev):
@@ -145,7 +161,9 @@ def attention_fwd(q: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.
     ``order_window`` > 0 re-orders only the last that many q-blocks of each XCD's range;
     ``q_order_out``: int32 [B*H*ceil(Lq/128)] to receive the dispatch permutation, for tests).
     ``persistent``: a resident-sized launch whose workgroups pull q-blocks from per-XCD queues
-    (work_queue(); scheduling only, the same outputs).
+    (work_queue(); scheduling only, the same outputs). While the current stream is being captured into
+    a graph and has no queue yet (no eager persistent call was made on it before the capture), the
+    call launches the one-workgroup-per-q-block form instead and creates no queue: the same bits.
     ``out_layout``: the memory order of the output allocated here: "bhld" (contiguous) or "blhd" (the
     [B,H,Lq,D] view of [B,Lq,H,D] memory, the projections' layout; the same values, stored through
     other strides). ``out``: a caller's [B,H,Lq,D] buffer instead, of any layout with unit d-stride,
@@ -196,8 +214,7 @@ def attention_fwd(q: torch.Tensor, k: Optional[torch.Tensor], v: Optional[torch.
     a.scale = float(scale) if scale else 0.0
     a.dtype = _dtype_code(q)
     a.heavy_rows = int(heavy_rows)
-    if persistent:
-        a.work_queue = work_queue(dev).data_ptr()
+    a.work_queue = _work_queue_ptr(dev, persistent)
     if order and block_mask is not None and use_main:
         nbq = (Lq + BLOCK - 1) // BLOCK
         q_order = q_order_out if q_order_out is not None else torch.empty(B * H * nbq, device=dev, dtype=torch.int32)
@@ -1477,6 +1494,9 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
     """vb_ml_attn_fwd: multi-level attention of q [B,H,L,D] over the KV pyramids. Returns out
     (rows through q_rows) and, if want_lse, the fp32 natural-log LSE [B,H,L] (at the caller's rows
     q_rows[g], like out: include/vblade.h).
+    ``persistent``: as attention_fwd: the work-queue launch, or, while the current stream is being
+    captured into a graph and has no queue yet, the one-workgroup-per-q-block form (the same bits; no
+    queue is created inside a capture).
     ``out_layout`` / ``out``: as attention_fwd."""
     io_layout_code("out_layout", out_layout)
     dev = _require_gpu(q, kpyr, vpyr, level_mask_u8, q_rows)
@@ -1509,8 +1529,7 @@ def ml_attention_fwd(q, kpyr, vpyr, level_mask_u8, *, q_rows=None, scale=None, r
     a.ref_tail = 1 if ref_tail else 0
     a.dtype = _dtype_code(q)
     a.heavy_rows = int(heavy_rows)
-    if persistent:
-        a.work_queue = work_queue(dev).data_ptr()
+    a.work_queue = _work_queue_ptr(dev, persistent)
     check(_lib.load().vb_ml_attn_fwd(ctypes.byref(a), _stream(dev)), "vb_ml_attn_fwd")
     return (out, lse) if want_lse else out
 
