@@ -626,9 +626,134 @@ def _branch_bwd(q, k, v, out, lse, dout, w, block_mask, scale, block, rdtype):
     return dq, dk, dv
 
 
+def kept_key_rows(mask_row, Lk, block=128):
+    """The key rows one q-block's mask row [>= ceil(Lk/block)] keeps, ascending, as the kernels' lists
+    hold them. A bool row keeps a block once; an integer row keeps block j ``mask_row[j]`` times (a
+    deliberately wrong list for testing the error metric: an entry counted twice)."""
+    nbk = (Lk + block - 1) // block
+    m = mask_row[:nbk]
+    blocks = torch.nonzero(m).flatten()
+    if m.dtype != torch.bool:
+        blocks = blocks.repeat_interleave(m[blocks].long())
+    rows = (blocks[:, None] * block + torch.arange(block)).flatten()
+    return rows[rows < Lk]
+
+
+def gathered_attention(q, k, v, block_mask, *, kp=None, vp=None, bias=0.0, use_main=True, sm_scale=None,
+                       block=128, emulate=None):
+    """joint_attention (``emulate`` None; fp64) or attention_fwd_emulated (``emulate`` = its keyword
+    arguments store_dtype, prescale_q, m_lag; fp32) for long sequences: per (b, h, q-block) the kept
+    key blocks are gathered, followed by the pooled keys, and the same arithmetic runs on them with
+    everything visible, so the work follows the mask's density instead of Lq x Lk. ``block_mask``
+    None = dense. A q-block without a key gives zero rows and -inf LSE. ``m_lag`` is [B,H,Lq,1] or
+    None. Returns (out, lse) as the dense form does."""
+    B, H, Lq, D = q.shape
+    scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(D)
+    Lk = k.shape[2] if use_main else 0
+    Lkp = 0 if kp is None else kp.shape[2]
+    nbq = (Lq + block - 1) // block
+    dt = torch.float64 if emulate is None else torch.float32
+    out = torch.zeros(B, H, Lq, D, dtype=dt)
+    lse = torch.full((B, H, Lq), float("-inf"), dtype=dt)
+    every = torch.arange(Lk)
+    m = None if block_mask is None else block_mask.expand(B, H, *block_mask.shape[2:])
+    if emulate is not None:
+        emulate = dict(emulate)
+        lag = emulate.pop("m_lag", None)
+        pooled_bias2 = float(np.float32(bias) * LOG2E_F32)
+    for b in range(B):
+        for h in range(H):
+            pk = () if kp is None else (kp[b:b + 1, h:h + 1],)
+            pv = () if kp is None else (vp[b:b + 1, h:h + 1],)
+            for i in range(nbq):
+                r0, r1 = i * block, min(Lq, (i + 1) * block)
+                rows = every if m is None else kept_key_rows(m[b, h, i], Lk, block)
+                n = rows.numel() * bool(use_main)
+                if n + Lkp == 0:
+                    continue
+                K = torch.cat(((k[b:b + 1, h:h + 1, rows],) if n else ()) + pk, 2)
+                V = torch.cat(((v[b:b + 1, h:h + 1, rows],) if n else ()) + pv, 2)
+                vis = torch.ones(1, 1, r1 - r0, n + Lkp, dtype=torch.bool)
+                qb = q[b:b + 1, h:h + 1, r0:r1]
+                if emulate is None:
+                    kb = torch.cat((torch.zeros(n, dtype=torch.float64), torch.full((Lkp,), float(bias), dtype=torch.float64)))
+                    o, l = softmax_over_visible(qb, K, V, vis, kb, scale)
+                else:
+                    kb = torch.cat((torch.zeros(n), torch.full((Lkp,), pooled_bias2)))
+                    o, l = fwd_emulated_over_visible(qb, K, V, vis, kb, scale, m_lag=None if lag is None else lag[b:b + 1, h:h + 1, r0:r1],
+                                                     **emulate)
+                out[b, h, r0:r1], lse[b, h, r0:r1] = o[0, 0], l[0, 0]
+    return out, lse
+
+
+def _branch_bwd_gathered(q, k, v, out, lse, dout, w, block_mask, scale, block, rdtype, kv_mask=None, full_tail=False):
+    """_branch_bwd for long sequences: per (b, h, q-block) the kept key blocks are gathered, the same
+    arithmetic with the same ``rdtype`` rounding points runs on them, and dk/dv are scatter-added.
+
+    Two deliberately wrong forms, for testing the error metric against the lists the kernels build:
+      * ``kv_mask`` (bool or integer counts, as kept_key_rows): the dK/dV side takes its (q-block,
+        key block) pairs from it while dQ keeps ``block_mask``'s, as a dK/dV kernel with a wrong
+        q-list would; an integer ``block_mask`` counts a key-list entry more than once in dQ.
+      * ``full_tail``: a last block of at most block/2 rows is treated as if its second half-tile held
+        block/2 more copies of the last row (the kernels skip that half-tile, ``ntiles -= 1``; their
+        loads clamp to the last row): the last key block's copies enter dQ, the last q-block's dK/dV."""
+    B, H, Lq, D = q.shape
+    Lk = k.shape[2]
+    R = (lambda t: t) if rdtype is None else (lambda t: t.to(rdtype).double())
+    qf, kf, vf, of, dof = (t.double() for t in (q, k, v, out, dout))
+    lse, w = lse.double(), w.double()
+    live = torch.isfinite(lse) & (w > 0)
+    lse_s = torch.where(live, lse, torch.zeros_like(lse))
+    w_s = torch.where(live, w, torch.zeros_like(w))
+    delta = (dof * of).sum(-1, keepdim=True)
+    dq = torch.zeros(B, H, Lq, D, dtype=torch.float64)
+    dk = torch.zeros(B, H, Lk, D, dtype=torch.float64)
+    dv = torch.zeros(B, H, Lk, D, dtype=torch.float64)
+    nbq = (Lq + block - 1) // block
+    half = block // 2
+    q_extra = full_tail and Lq - (nbq - 1) * block <= half
+    k_extra = full_tail and Lk - (Lk - 1) // block * block <= half
+    if block_mask is None:
+        block_mask = torch.ones(1, 1, nbq, (Lk + block - 1) // block, dtype=torch.bool)
+    m = block_mask.expand(B, H, *block_mask.shape[2:])
+    mkv = None if kv_mask is None else kv_mask.expand(B, H, *kv_mask.shape[2:])
+
+    def products(b, h, qrows, krows):
+        """(dS, w*P, K rows, V rows) of the query rows ``qrows`` against the key rows ``krows``."""
+        Kg, Vg = kf[b, h, krows], vf[b, h, krows]
+        s = torch.matmul(qf[b, h, qrows], Kg.transpose(-1, -2)) * scale
+        p = torch.exp(s - lse_s[b, h, qrows, None]) * w_s[b, h, qrows, None]
+        ds = R(p * (torch.matmul(dof[b, h, qrows], Vg.transpose(-1, -2)) - delta[b, h, qrows]))
+        return ds, R(p), Kg
+
+    for b in range(B):
+        for h in range(H):
+            for i in range(nbq):
+                qrows = torch.arange(i * block, min(Lq, (i + 1) * block))
+                krows = kept_key_rows(m[b, h, i], Lk, block)
+                split = mkv is not None and not torch.equal(mkv[b, h, i].long(), m[b, h, i].long())
+                if krows.numel():
+                    kq = krows
+                    if k_extra and int(krows[-1]) == Lk - 1:
+                        kq = torch.cat((krows, torch.full((half,), Lk - 1)))
+                    ds, p, Kg = products(b, h, qrows, kq)
+                    dq[b, h, qrows] = torch.matmul(ds, Kg) * scale
+                last_q = q_extra and i == nbq - 1
+                if split or last_q or (krows.numel() and kq is not krows):
+                    krows = kept_key_rows(mkv[b, h, i], Lk, block) if split else krows
+                    if last_q:
+                        qrows = torch.cat((qrows, torch.full((half,), Lq - 1)))
+                    if krows.numel():
+                        ds, p, _ = products(b, h, qrows, krows)
+                if krows.numel():
+                    dk[b, h].index_add_(0, krows, torch.matmul(ds.transpose(-1, -2), qf[b, h, qrows]) * scale)
+                    dv[b, h].index_add_(0, krows, torch.matmul(p.transpose(-1, -2), dof[b, h, qrows]))
+    return dq, dk, dv
+
+
 def two_branch_attention_bwd(q_r, k_r, v_r, kp, vp, out1, lse1, out2, lse2, alpha, dout, mask, gap,
                              sm_scale=None, store_dtype=torch.bfloat16, emulate_rounding=False,
-                             block=128, replicate_fold=True):
+                             block=128, replicate_fold=True, gathered=False, kv_mask=None, full_tail=False):
     """Op-level statement of vb_attn_bwd (include/vblade.h), every tensor in REORDERED row order:
     the gradient w.r.t. q_r [B,H,Lq,D], k_r, v_r [B,H,Lk,D] of
         alpha * BSA(q_r, k_r, v_r; mask)  +  storage(1 - alpha) * SDPA(q_r, pool(k_r), pool(v_r))
@@ -644,13 +769,21 @@ def two_branch_attention_bwd(q_r, k_r, v_r, kp, vp, out1, lse1, out2, lse2, alph
     operands), and the three results (dq of both branches, dk/dv after the pool fold, summed in the
     accumulator and rounded once). ``replicate_fold=False`` drops the replicate-padding term of the
     mean-pool adjoint: a deliberately wrong reference for testing the error metric.
+    ``gathered``: the main branch through _branch_bwd_gathered (long sequences under a sparse mask: the
+    same arithmetic on each q-block's kept key blocks; equal to the dense form up to fp64 summation
+    order); the pooled branch stays dense (Lkp is small). ``kv_mask`` and ``full_tail`` are that
+    function's deliberately wrong lists.
     Returns fp32 (dq_r, dk_r, dv_r)."""
     D = q_r.shape[-1]
     Lk = k_r.shape[2]
     scale = sm_scale if sm_scale is not None else 1.0 / math.sqrt(D)
     rd = store_dtype if emulate_rounding else None
     w1 = torch.ones(q_r.shape[:3]) if alpha is None else alpha.float()
-    dq, dk, dv = _branch_bwd(q_r, k_r, v_r, out1, lse1, dout, w1, mask, scale, block, rd)
+    if gathered:
+        dq, dk, dv = _branch_bwd_gathered(q_r, k_r, v_r, out1, lse1, dout, w1, mask, scale, block, rd, kv_mask, full_tail)
+    else:
+        assert kv_mask is None and not full_tail
+        dq, dk, dv = _branch_bwd(q_r, k_r, v_r, out1, lse1, dout, w1, mask, scale, block, rd)
     if kp is not None:
         w2 = rnd(1.0 - w1, store_dtype)
         dq2, dkp, dvp = _branch_bwd(q_r, kp, vp, out2, lse2, dout, w2, None, scale, block, rd)

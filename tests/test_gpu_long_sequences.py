@@ -286,7 +286,8 @@ def test_module_runs_at_the_wan_720p_grid(ops):
 @gpu
 def test_module_under_autograd_past_320_blocks(ops):
     """321 blocks under autograd (the two-branch path): dq/dk/dv of the run that predicts its mask
-    equal, bit for bit, those of the run handed that mask through block_mask=."""
+    equal, bit for bit, those of the run handed that mask through block_mask=, and hold the per-row
+    bound (2 x the rounding emulation's worst row) against the gathered fp64 two-branch reference."""
     import vblade
     L, D = 41000, 64
     m = vblade.AdaptiveBlockSparseAttn("cog", width=58, height=37, depth=19, log_every=0)   # + 226 text rows
@@ -307,6 +308,31 @@ def test_module_under_autograd_past_320_blocks(ops):
     second = run(block_mask=mask)
     for a, b in zip(first, second):
         assert torch.isfinite(a.float()).all() and torch.equal(a, b)
+
+    # both runs launch the same kernels, so a wrong block list would agree with itself: the gradients
+    # per row against the gathered two-branch reference (tests/long_bwd_cases.py), which gets the
+    # reordered inputs, the module's mask and the device's own out/lse/alpha, recomputed here by
+    # _AdaptiveSplitFn.forward's calls and tied to the module's run by the combined output's bits
+    import long_bwd_cases as C
+    from conftest import record
+    rows, gap = m._rows(base[0].device), m.sample_gap
+    q, k, v, do = base
+    kp, vp, k_r, v_r = ops.pool_kv(k, v, gap, rows, reordered=True)
+    out2, lse2 = ops.attention_fwd(q, None, None, use_main=False, q_rows=rows, kp=kp, vp=vp, need_lse=True)
+    out1, lse1 = ops.attention_fwd(q, k_r, v_r, block_mask=mask, q_rows=rows, need_lse=True, heavy_rows=m.force_tail)
+    out, alpha = ops.lse_combine(out1, lse1, out2, lse2, gap)
+    assert torch.equal(out, first[0])
+    P = rows.long().cpu()
+    lq = lambda t: t.cpu()[:, :, P]  # noqa: E731
+    ref, emu = C.backward_reference(lq(q), k_r.cpu(), v_r.cpu(), lq(do), lq(out1), lq(lse1), mask.bool().cpu(), BF16,
+                                    kp=kp.cpu(), vp=vp.cpu(), out2=lq(out2), lse2=lq(lse2), alpha=lq(alpha), gap=gap)
+    facts = []
+    for name, g, r, e in zip(("dq", "dk", "dv"), first[1:], ref, emu):
+        bound = O.per_row_bound(e, r, BF16)
+        worst, where = O.per_row_error(lq(g.float()), r)
+        facts.append(f"{name} {worst:.2e}/{bound / 2:.2e}")
+        assert worst <= bound, (name, worst, where, bound)
+    record("module under autograd at 321 blocks, worst row: gpu/emulation (bound: 2x emulation)", " ".join(facts))
 
 
 # ------------------------------------------------------------------ 7. CPU: the entry's validation
